@@ -5,12 +5,18 @@ Default workload `s2anet_train` = BASELINE.json's headline: S2ANet-R50-FPN train
 tiles, 2 images per GPU, 64 random OBB gts per image, random-init weights of the reference architecture
 (configs/s2anet/s2anet_r50_fpn_1x_dota.py), fp32 like the reference, SGD + clip + StepLR, DDP/RCCL gradient
 all-reduce when launched on N > 1 ranks (weak scaling: per-GPU batch fixed).  `value` = img/s over all ranks.
-The same line carries
+
+A plain run sets up, runs W untimed and K timed steps, writes what the last timed step computed when
+`--dump-outputs DIR` is given (DIR/<name>.npy, float32 / float64, at most 64 MB: a fixed seeded sample of a larger
+array; a train workload's last timed step then starts again from the seeded initial weights, so that runs agree) and
+prints the line.  With `--full` the same line also carries
   * `roofline`: the path's HBM-bound hand-written kernel, rotated RoIAlign forward at the north-star point
     (1x256x256x256 fp32 map = stride-4 level of a 1024x1024 tile, 2000 RoIs, 7x7, sampling 2), measured live in
     this process with HIP events on the launch stream.  ALGORITHMIC bytes per launch:
     4*N*C*H*W + 4*R*C*PH*PW + 24*R = 67.11 + 100.35 + 0.05 MB = 167.5 MB;
-  * `cpu_baseline`: the CPU oracle (kind "port") on that same RoIAlign workload on all host cores.
+  * `cpu_baseline`: the CPU oracle (kind "port") on that same RoIAlign workload on all host cores;
+  * the rest of the roofline leg (cold-map rate, live counter traffic, the backward legs, the reference's CPU sources)
+    and `secondary`: ms/step of the other BASELINE.json model configs.
 
 Other workloads (`--workload`): roi_align_rotated (the roofline leg as its own line), roi_align_rotated_bwd,
 box_iou_rotated, nms_rotated, retinanet_infer (BASELINE configs[1]).
@@ -28,6 +34,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBPS = 8000.0  # MI355X_MICROARCH.md: 8 TB/s spec (6.29 TB/s measured copy)
+MIOPEN_TUNING_ITERATIONS = 30   # candidates per tunable MIOpen solver in the first step's search (see main)
 
 
 def parse():
@@ -41,11 +48,15 @@ def parse():
     p.add_argument("--size", type=int, default=1024, help="tile size (s2anet_train)")
     p.add_argument("--amp", default="none", choices=["none", "bf16", "fp16"])
     p.add_argument("--rois", type=int, default=2000)
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="after the headline: the roofline leg, the CPU baselines and the other model configs")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step computed as DIR/<name>.npy")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="(--full) leave out the CPU baselines")
     p.add_argument("--no-live-traffic", action="store_true",
-                   help="roofline.traffic from profiles/hbm_traffic.json instead of two rocprofv3 --pmc passes run now")
+                   help="(--full) roofline.traffic from profiles/hbm_traffic.json instead of two rocprofv3 --pmc passes run now")
     p.add_argument("--no-secondary", action="store_true",
-                   help="leave out the `secondary` object (ms/step of the other BASELINE.json model configs)")
+                   help="(--full) leave out the `secondary` object (ms/step of the other BASELINE.json model configs)")
     a = p.parse_args()
     if a.batch is None:
         a.batch = 4 if a.workload == "roitrans_train" else 2      # configs[4]: batch 32 over 8 GPUs
@@ -194,7 +205,7 @@ def make_step(workload, d):
     if workload == "roi_align_rotated_bwd":
         feat, rois, grad = d["feat"], d["rois"], d["grad"]
         R = rois.shape[0]
-        gin = torch.empty_like(feat)
+        gin = d["grad_in"] = torch.empty_like(feat)
         cl = os.environ.get("JDET_BENCH_BWD_LAYOUT", "cl") == "cl"   # grad_out channels-last (what the tile forward pairs with)
         if cl:
             grad = grad.contiguous(memory_format=torch.channels_last)
@@ -223,7 +234,7 @@ def make_step(workload, d):
         feat, rois = d["feat"], d["rois"]
         R = rois.shape[0]
         grad = d["grad"].contiguous(memory_format=torch.channels_last)
-        gin = torch.empty_like(feat)
+        gin = d["grad_in"] = torch.empty_like(feat)
         out = torch.empty((R, 256, 7, 7), device=feat.device, memory_format=torch.channels_last)
         pb = lib.jdet_roi_align_backward_plan_bytes(0, R, 1, 256, 256, 7, 7, 2)
         plan = torch.empty((pb,), dtype=torch.uint8, device=feat.device)
@@ -304,8 +315,20 @@ def make_train(a, rank, dev):
     images = images.contiguous(memory_format=torch.channels_last)
 
     def step():
-        runner.train_step(images, targets)
+        return runner.train_step(images, targets)
     return step, runner
+
+
+def restart_train(runner, init):
+    """the runner back at the weights `init` with zeroed momentum buffers: for a momentum SGD without dampening the next
+    step applies the first step's update rule (buf = gradient), so it computes what a first step from `init` computes"""
+    with torch.no_grad():
+        for p, p0 in zip(runner.model.parameters(), init):
+            p.copy_(p0)
+        for st in runner.optimizer.state.values():
+            buf = st.get("momentum_buffer")
+            if buf is not None:
+                buf.zero_()
 
 
 def make_retinanet_infer(a, rank, dev):
@@ -636,6 +659,51 @@ def secondary_lines(a, dev):
     return out
 
 
+DUMP_BUDGET = 64 * 2 ** 20       # bytes --dump-outputs writes at most, all arrays together
+DUMP_ARRAY_BYTES = 16 * 2 ** 20  # an array larger than this is written as a fixed seeded sample of this size
+
+
+def output_arrays(obj, name):
+    """(name, array) for every tensor / ndarray / number in a nest of tuples, lists and dicts, in a fixed order"""
+    if torch.is_tensor(obj) or isinstance(obj, (np.number, int, float, bool)) or \
+            (isinstance(obj, np.ndarray) and obj.dtype.kind in "biuf"):
+        return [(name, obj)]
+    if isinstance(obj, dict):
+        items = obj.items()
+    elif isinstance(obj, (list, tuple)):
+        items = enumerate(obj)
+    else:
+        return []
+    out = []
+    for k, v in items:
+        out += output_arrays(v, "%s.%s" % (name, k))
+    return out
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every (name, array) as DIR/<name>.npy -- float64 if it is float64 or integer / bool, float32
+    otherwise.  An array of more than DUMP_ARRAY_BYTES is written flattened as a stratified sample: one element drawn
+    from each of k equal strata by a generator seeded 0, so the same shape gives the same indices in every run."""
+    os.makedirs(dirname, exist_ok=True)
+    left = DUMP_BUDGET
+    for name, x in arrays:
+        t = torch.as_tensor(x).detach()
+        dt = torch.float32 if t.is_floating_point() and t.dtype != torch.float64 else torch.float64
+        size = torch.finfo(dt).bits // 8
+        k = min(DUMP_ARRAY_BYTES, left) // size
+        if k < 1:
+            raise SystemExit("bench.py: --dump-outputs would exceed %d bytes at %s" % (DUMP_BUDGET, name))
+        if t.numel() > k:
+            n = t.numel()
+            stride = n // k
+            idx = np.arange(k, dtype=np.int64) * stride + np.random.default_rng(0).integers(0, stride, k)
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        a = t.to(dt).cpu().numpy()
+        left -= a.nbytes
+        safe = "".join(c if c.isalnum() or c in "._-" else "_" for c in name)
+        np.save(os.path.join(dirname, safe + ".npy"), a)
+
+
 def launch_command(argv, gpus, port=None):
     """`python bench.py --gpus N ...` started by hand (no WORLD_SIZE in the environment): the command that runs the
     same arguments as N ranks of one node, one rank per GPU, rendezvous on 127.0.0.1."""
@@ -691,6 +759,10 @@ def main():
               file=sys.stderr)
     if a.workload == "selftest_cpu":
         return selftest_cpu(a, world, rank)
+    # The Runner's conv autotune has MIOpen search every tunable solver's whole configuration space at the first step
+    # (~25 s in a fresh home, where no tuning database exists yet).  The bench bounds each search; a value set in the
+    # environment wins.
+    os.environ.setdefault("MIOPEN_DEBUG_TUNING_ITERATIONS_MAX", str(MIOPEN_TUNING_ITERATIONS))
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs a HIP device (no CPU fallback in the product path)")
     torch.cuda.set_device(local)
@@ -710,7 +782,18 @@ def main():
             step, runner = make_retinanet_infer(a, rank, dev)
             per_step = 1
             title = "img/s RetinaNet-OBB R50-FPN inference (incl. rotated NMS), %dx%d synthetic tile" % (a.size, a.size)
-        t, dev_ms = timed(step, a.steps, a.warmup, dist, dev)
+        last, calls, total = [None], [0], a.warmup + a.steps
+        # --dump-outputs: the float-atomic weight gradients make chained train steps drift apart from run to run, so the
+        # last timed step starts again from the seeded initial weights with zeroed momentum (the first step's rule)
+        init = ([p.detach().clone() for p in runner.model.parameters()]
+                if a.dump_outputs and a.workload in TRAIN_WORKLOADS and total > 1 else None)
+
+        def timed_step():       # the step, keeping what it returned (--dump-outputs writes the last timed one)
+            calls[0] += 1
+            if init is not None and calls[0] == total:
+                restart_train(runner, init)
+            last[0] = step()
+        t, dev_ms = timed(timed_step, a.steps, a.warmup, dist, dev)
         if rank == 0:
             line = {
                 "metric": title,
@@ -729,25 +812,37 @@ def main():
                             "post": "top-2000/level -> decode -> multiclass rotated NMS (thr 0.1) -> polys",
                             "parallelism": "replicas x%d (no collective)" % world}),
             }
-            # roofline leg: the path's HBM-bound hand-written kernel at the north-star point, measured live
-            d = make_inputs("roi_align_rotated", a.rois, 1000, dev)
-            rstep, _, _, nbytes, kname, _ = make_step("roi_align_rotated", d)
-            _, rms = timed(rstep, 200, 20, None, dev)
-            line["roofline"] = roofline_obj("roi_align_rotated", nbytes, rms, kname, dev)
-            if world == 1 and not a.no_cpu_baseline:
-                cb = cpu_baseline("roi_align_rotated", d, a.rois)
-                cb["sample"] = "rotated RoIAlign forward leg (the roofline kernel), not the whole train step: " + cb["sample"]
-                line["cpu_baseline"] = cb
-            if world == 1:
-                del rstep
-                roofline_extras(a, dev, line, live=not a.no_live_traffic)
-                rstep = None
-            if world == 1 and a.workload == "s2anet_train" and a.amp == "none" and not a.no_secondary:
-                del step, runner, rstep, d
-                import gc
-                gc.collect()
-                torch.cuda.empty_cache()
-                line["secondary"] = secondary_lines(a, dev)
+            if a.dump_outputs:
+                if a.workload in TRAIN_WORKLOADS:
+                    # the loss and its parts, and (a sample of) the parameters the step updated in place
+                    loss, parts = last[0]
+                    params = torch.cat([p.detach().reshape(-1) for p in runner.model.parameters()])
+                    dump_outputs(a.dump_outputs, [("loss", loss)] + sorted(parts.items()) + [("params", params)])
+                    del params
+                else:
+                    dump_outputs(a.dump_outputs, output_arrays(last[0], "detections"))
+            last[0] = init = None
+            del timed_step
+            if a.full:
+                # roofline leg: the path's HBM-bound hand-written kernel at the north-star point, measured live
+                d = make_inputs("roi_align_rotated", a.rois, 1000, dev)
+                rstep, _, _, nbytes, kname, _ = make_step("roi_align_rotated", d)
+                _, rms = timed(rstep, 200, 20, None, dev)
+                line["roofline"] = roofline_obj("roi_align_rotated", nbytes, rms, kname, dev)
+                if world == 1 and not a.no_cpu_baseline:
+                    cb = cpu_baseline("roi_align_rotated", d, a.rois)
+                    cb["sample"] = "rotated RoIAlign forward leg (the roofline kernel), not the whole train step: " + cb["sample"]
+                    line["cpu_baseline"] = cb
+                if world == 1:
+                    del rstep
+                    roofline_extras(a, dev, line, live=not a.no_live_traffic)
+                    rstep = None
+                if world == 1 and a.workload == "s2anet_train" and a.amp == "none" and not a.no_secondary:
+                    del step, runner, rstep, d
+                    import gc
+                    gc.collect()
+                    torch.cuda.empty_cache()
+                    line["secondary"] = secondary_lines(a, dev)
             print(json.dumps(line))
     else:
         d = make_inputs(a.workload, a.rois, 1000 + rank, dev)
@@ -767,12 +862,16 @@ def main():
                            "pooled": "7x7", "sampling_ratio": 2, "spatial_scale": 0.25,
                            "parallelism": "image-parallel x%d (no collective)" % world},
             }
-            line["roofline"] = roofline_obj(a.workload, nbytes, dev_ms, kname, dev)
-            if world == 1 and not a.no_cpu_baseline:
-                line["cpu_baseline"] = cpu_baseline(a.workload, d, a.rois)
-            if world == 1 and a.workload == "roi_align_rotated" and not a.no_live_traffic and \
-                    os.environ.get("JDET_ROI_FWD_PATH", "roi_cl") == "roi_cl":
-                roofline_extras(a, dev, line, live=True)
+            if a.dump_outputs:
+                dump_outputs(a.dump_outputs, [(k, d[k]) for k in ("out", "grad_in") if torch.is_tensor(d.get(k))])
+            # the timed kernel's own rate against the HBM peak; --full adds the copy rate measured on this device
+            line["roofline"] = roofline_obj(a.workload, nbytes, dev_ms, kname, dev if a.full else None)
+            if a.full:
+                if world == 1 and not a.no_cpu_baseline:
+                    line["cpu_baseline"] = cpu_baseline(a.workload, d, a.rois)
+                if world == 1 and a.workload == "roi_align_rotated" and not a.no_live_traffic and \
+                        os.environ.get("JDET_ROI_FWD_PATH", "roi_cl") == "roi_cl":
+                    roofline_extras(a, dev, line, live=True)
             print(json.dumps(line))
     if dist is not None:
         dist.destroy_process_group()

@@ -5,9 +5,9 @@ set -x
 R=$PWD; O=$R/gpurun_out/final; mkdir -p $O
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1
 timeout 1500 python -m pytest tests -m gpu -q 2>&1 | tail -3
-timeout 600 python bench.py > $O/bench_default.json 2> $O/bench_default.err; tail -1 $O/bench_default.json | cut -c1-400
+timeout 600 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; tail -1 $O/bench_default.json | cut -c1-400
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats -f csv -d $O/trace -o t -- python $R/bench.py --steps 8 --warmup 4 --no-cpu-baseline --no-secondary > $O/trace.log 2>&1
+rocprofv3 --kernel-trace --stats -f csv -d $O/trace -o t -- python $R/bench.py --steps 8 --warmup 4 --full --no-live-traffic --no-cpu-baseline --no-secondary > $O/trace.log 2>&1
 cd $R
 f=$(find $O/trace -name '*kernel_trace.csv' | head -1)
 python scripts/steady_state.py $f assign_anchor_kernel 4 5 120 > $O/steady_state.txt; head -2 $O/steady_state.txt | cut -c1-160

@@ -185,8 +185,8 @@ OUT=$R/gpurun_out/r4_final; mkdir -p $OUT
 export TMPDIR=/tmp
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1
 timeout 2400 python -m pytest tests -m gpu -q > $OUT/pytest_gpu.log 2>&1; tail -2 $OUT/pytest_gpu.log
-timeout 900 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; tail -1 $OUT/bench_default.json | cut -c1-900
-(cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_default -o t -- python $R/bench.py --steps 8 --warmup 4 --no-cpu-baseline --no-secondary > $OUT/trace_default.log 2>&1)
+timeout 900 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; tail -1 $OUT/bench_default.json | cut -c1-900
+(cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_default -o t -- python $R/bench.py --steps 8 --warmup 4 --full --no-live-traffic --no-cpu-baseline --no-secondary > $OUT/trace_default.log 2>&1)
 f=$(find $OUT/trace_default -name '*kernel_trace.csv' | head -1)
 python scripts/steady_state.py $f assign_anchor_kernel 4 5 120 > $OUT/steady_state_s2anet.txt 2>&1
 head -3 $OUT/steady_state_s2anet.txt | cut -c1-160
@@ -395,7 +395,7 @@ timeout 600 python -m pytest tests/test_gpu_roi_align.py tests/test_gpu_s2anet.p
 run_n() {
 timeout 900 python scripts/convergence_check.py 2>&1 | grep -v Warning | tail -8
 timeout 2400 python -m pytest tests -m gpu -q 2>&1 | tail -2
-timeout 600 python bench.py 2>/dev/null | tail -1 | cut -c1-700
+timeout 600 python bench.py --full 2>/dev/null | tail -1 | cut -c1-700
 }
 
 run_o() {
@@ -502,7 +502,7 @@ run_w() {
 # round 4: re-validation after the forward mode 3 commit: smoke, full GPU suite, default bench line
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1
 timeout 2400 python -m pytest tests -m gpu -q 2>&1 | tail -3
-timeout 900 python bench.py 2>/dev/null | tail -1 | cut -c1-400
+timeout 900 python bench.py --full 2>/dev/null | tail -1 | cut -c1-400
 }
 
 run_x() {

@@ -83,9 +83,9 @@ run_final() {
 OUT=$R/gpurun_out/r5_final; mkdir -p $OUT
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1
 timeout 2400 python -m pytest tests -m gpu -q > $OUT/pytest_gpu.log 2>&1; tail -3 $OUT/pytest_gpu.log
-timeout 1200 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; tail -1 $OUT/bench_default.json | cut -c1-2600
+timeout 1200 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; tail -1 $OUT/bench_default.json | cut -c1-2600
 grep -c "AccumulateGrad" $OUT/bench_default.err
-(cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_default -o t -- python $R/bench.py --steps 8 --warmup 4 --no-cpu-baseline --no-secondary > $OUT/trace_default.log 2>&1)
+(cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_default -o t -- python $R/bench.py --steps 8 --warmup 4 --full --no-live-traffic --no-cpu-baseline --no-secondary > $OUT/trace_default.log 2>&1)
 f=$(find $OUT/trace_default -name '*kernel_trace.csv' | head -1)
 python scripts/steady_state.py $f assign_anchor_kernel 4 5 120 > $OUT/steady_state_s2anet.txt 2>&1
 head -3 $OUT/steady_state_s2anet.txt | cut -c1-160
@@ -150,14 +150,14 @@ run_i() {   # closing re-validation: two-rank tests, 16-deep K steps on the shor
   OUT=$R/gpurun_out/r5_i; mkdir -p $OUT
   timeout 900 python -m pytest tests/test_gpu_ddp_detectors.py tests/test_gpu_frozen_bn.py -q 2>&1 | tail -4 | tee $OUT/pytest.txt
   timeout 600 python scripts/conv_bn_timing.py tiles 2>&1 | grep -v Warning | tee $OUT/tiles.txt
-  timeout 1200 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; tail -1 $OUT/bench_default.json | cut -c1-400
+  timeout 1200 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; tail -1 $OUT/bench_default.json | cut -c1-400
   grep -c "AccumulateGrad\|Grad strides" $OUT/bench_default.err
 }
 
 run_j() {   # prediction convs through conv_module + 16-deep K steps: model suites, the bench line, the step profile
   OUT=$R/gpurun_out/r5_j; mkdir -p $OUT
   timeout 1200 python -m pytest tests/test_gpu_s2anet.py tests/test_gpu_head_parity.py tests/test_gpu_oriented_rcnn.py tests/test_gpu_roi_transformer.py tests/test_gpu_conv_bn.py tests/test_gpu_conv_igemm.py tests/test_gpu_configs_full_size.py tests/test_gpu_ddp_detectors.py -q 2>&1 | tail -4 | tee $OUT/pytest.txt
-  timeout 1200 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; tail -1 $OUT/bench_default.json | cut -c1-400
+  timeout 1200 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; tail -1 $OUT/bench_default.json | cut -c1-400
   bash scripts/gpu_prof_s2anet.sh > $OUT/prof.txt 2>&1; cp gpurun_out/prof_s2anet/steady_state.txt $OUT/steady_state.txt; head -3 $OUT/steady_state.txt | cut -c1-150
   rm -rf gpurun_out/prof_s2anet/trace
 }
@@ -201,7 +201,7 @@ run_z() {   # closing validation of the final tree: smoke, the whole GPU suite, 
   OUT=$R/gpurun_out/r5_z; mkdir -p $OUT
   timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1
   timeout 2400 python -m pytest tests -m gpu -q > $OUT/pytest_gpu.log 2>&1; tail -3 $OUT/pytest_gpu.log
-  timeout 1200 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; tail -1 $OUT/bench_default.json | cut -c1-300
+  timeout 1200 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; tail -1 $OUT/bench_default.json | cut -c1-300
   grep -c "AccumulateGrad\|Grad strides" $OUT/bench_default.err
   true
 }

@@ -83,6 +83,12 @@ def test_grid_anchors_and_alignconv_zero_offset():
     np.testing.assert_allclose(off[1], 2, atol=1e-5)   # dx of tap 0
 
 
+def config_fixture(rel):
+    """the recorded settings of the reference's config file `rel` (tests/golden/gen_configs.py)"""
+    stem = os.path.splitext(os.path.basename(rel))[0]
+    return os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "configs", stem + ".yaml")
+
+
 def test_registry_and_reference_config_build():
     """the registry names the named configs use resolve, and the reference's S2ANet config builds unchanged"""
     import jdet_amd.models  # noqa: F401
@@ -99,11 +105,8 @@ def test_registry_and_reference_config_build():
     with pytest.raises(AssertionError):
         R.BOXES.get("NoSuchThing")
     assert R.build_from_cfg(None, R.BOXES) is None
-    cfg_path = "/root/reference/configs/s2anet/s2anet_r50_fpn_1x_dota.py"
-    if not os.path.exists(cfg_path):
-        pytest.skip("reference configs not present on this box")
     from jdet_amd.config import Config
-    c = Config(cfg_path)
+    c = Config(config_fixture("configs/s2anet/s2anet_r50_fpn_1x_dota.py"))
     assert c.model.bbox_head.train_cfg.fam_cfg.assigner.type == "MaxIoUAssigner" and c.nothing is None
     m = R.build_from_cfg(c.model, R.MODELS)
     assert type(m).__name__ == "S2ANet"
@@ -138,12 +141,9 @@ REFERENCE_CONFIGS = [
 
 @pytest.mark.parametrize("rel,model_type,head_type", REFERENCE_CONFIGS)
 def test_the_four_named_reference_configs_build_unchanged(rel, model_type, head_type):
-    """the config files BASELINE.json names load through `Config` as they are and their model / optimizer / scheduler
-    sections build through the registries (build container only: the reference tree is not on the GPU box, where
-    jdet_amd.config.named carries the same sections as dicts)"""
-    path = os.path.join("/root/reference", rel)
-    if not os.path.exists(path):
-        pytest.skip("reference configs not present on this box")
+    """the config files BASELINE.json names, as `Config` reads them (tests/golden/configs/, recorded from the reference
+    by tests/golden/gen_configs.py): their model / optimizer / scheduler sections build through the registries"""
+    path = config_fixture(rel)
     import jdet_amd.models  # noqa: F401
     import jdet_amd.optims  # noqa: F401
     from jdet_amd.config import Config
