@@ -430,6 +430,53 @@ int jdet_smooth_l1_loss_level(const float* pred, const float* target, long targe
 int jdet_loss_grad_scale(const float* unit_grad, long n, const float* grad_out, const float* avg_factor,
                          float loss_weight, float* out, jdet_stream_t stream);
 
+/* Gaussian box losses of one pyramid level as one node (round 7, csrc/gaussian_loss.hip): replaces GDLoss
+ * (models/losses/gaussian_dist_loss.py:L48-276), GDLoss_v1 (gaussian_dist_loss_v1.py:L48-156) and KFLoss
+ * (kf_iou_loss.py:L48-99) with the decode in front of them (rotated_retina_head.py `reg_decoded_bbox`,
+ * kfiou_rotated_retina_head.py:L96-104).  Contract of jdet_smooth_l1_loss_level:
+ *   - pred (rows, 5) contiguous DELTAS; target / weight (rows, 5) behind blocked row indices (a level's window of the
+ *     per-image (N, A, 5) arrays read in place); weight NULL = every row.  A row counts when weight.mean(-1) > 0; the
+ *     weight is a mask only, never a factor (as in the reference).
+ *   - anchors (anchor_rows, 5), row r reads anchor r % anchor_rows; needed when decode_pred / decode_target is set.
+ *     decode_pred: the Gaussian of the prediction is that of delta2bbox_rotated(anchor, pred) (bit-identical
+ *     arithmetic to jdet_delta2bbox_rotated, means / stds / wh_ratio_clip of the params); decode_target: likewise for
+ *     the target (KFLoss's targets_decode).  KFIoU's smooth-L1 term always reads the undecoded xy deltas.
+ *   - *loss = (sum over counted rows / *avg_factor) * loss_weight; grad_pred = d sum / d pred (unit gradient, zero on
+ *     rows that do not count); the backward is jdet_loss_grad_scale.  KFIoU: det(Sigma) <= 0 gives Vb = 0 (the
+ *     reference's NaN -> 0) with a zero gradient.  Workspace: the focal-loss query.  Deterministic. */
+#define JDET_GD_GWD 0         /* GDLoss    gwd_loss        */
+#define JDET_GD_KLD 1         /* GDLoss    kld_loss        */
+#define JDET_GD_JD 2          /* GDLoss    jd_loss         */
+#define JDET_GD_KLD_SYMMAX 3  /* GDLoss    kld_symmax_loss */
+#define JDET_GD_KLD_SYMMIN 4  /* GDLoss    kld_symmin_loss */
+#define JDET_GD1_GWD 5        /* GDLoss_v1 gwd_loss        */
+#define JDET_GD1_KLD 6        /* GDLoss_v1 kld_loss        */
+#define JDET_GD1_BCD 7        /* GDLoss_v1 bcd_loss        */
+#define JDET_KFIOU 8          /* KFLoss    kfiou_loss      */
+#define JDET_GD_FUN_NONE 0    /* 'none' (GDLoss, KFLoss), '' (GDLoss_v1) */
+#define JDET_GD_FUN_LOG1P 1
+#define JDET_GD_FUN_SQRT 2
+#define JDET_GD_FUN_LN 3      /* KFLoss */
+#define JDET_GD_FUN_EXP 4     /* KFLoss */
+
+typedef struct jdet_gaussian_loss_params {
+  int kind;            /* JDET_GD_* / JDET_GD1_* / JDET_KFIOU */
+  int fun;             /* JDET_GD_FUN_* */
+  float tau, alpha;    /* GDLoss / GDLoss_v1 */
+  int normalize;       /* GDLoss gwd */
+  int sqrt_dist;       /* GDLoss kld, jd, kld_symmax, kld_symmin: the `sqrt` argument */
+  float beta, eps;     /* KFLoss */
+  int decode_pred, decode_target;
+  float means[5], stds[5], wh_ratio_clip;
+} jdet_gaussian_loss_params_t;
+
+int jdet_gaussian_loss_level(const float* pred, const float* target, long target_rows_per_block,
+                             long target_block_stride, const float* weight, long weight_rows_per_block,
+                             long weight_block_stride, const float* anchors, long anchor_rows, long rows,
+                             const jdet_gaussian_loss_params_t* params, const float* avg_factor, float loss_weight,
+                             float* loss, float* grad_pred, void* workspace, size_t workspace_bytes,
+                             jdet_stream_t stream);
+
 /* Head glue as a single pass (csrc/level_pack.hip; round 6).
  * jdet_level_pack_nhwc: the small pyramid levels of a weight-shared tower (S2ANetHead.execute runs its towers per level,
  *   models/roi_heads/s2anet_head.py:L207-252; here they run once on a packed canvas) -- levels[l] (N, h_l, w_l, C)
@@ -557,6 +604,18 @@ int jdet_anchor_targets_rotated(const float* anchors, const float* gt, const int
                                 const float* stds5, float pos_weight, int32_t* labels,
                                 float* label_weights, float* bbox_targets, float* bbox_weights,
                                 int32_t* num_pos, jdet_stream_t stream);
+/* The same for `reg_decoded_bbox=True` (anchor_target.py:L79-80): the box target of a positive anchor is its assigned
+ * gt box itself (a copy), zeros elsewhere; labels, label weights, box weights and *num_pos as above.  Lets the dense
+ * (sync-free, fixed-shape) target path serve the decoded-box losses (round 7). */
+int jdet_anchor_targets_rotated_boxes(const float* gt, const int32_t* gt_labels, const int32_t* gt_inds, int A, int K,
+                                      float pos_weight, int32_t* labels, float* label_weights, float* bbox_targets,
+                                      float* bbox_weights, int32_t* num_pos, jdet_stream_t stream);
+
+/* FakeBboxOverlaps2D_rotated's conversion (models/boxes/iou_calculator.py:L108-110): out (n, 5) =
+ * hbb2obb(obb2hbb(boxes)) (ops/bbox_transforms.py:L639-645, L653-665) -- the enclosing horizontal box as an OBB,
+ * (w, h, 0) when w >= h else (h, w, -pi/2); boxes (n, stride >= 5) rows, n = 0: no-op whatever the stride.  One
+ * launch (round 7). */
+int jdet_obb2hbb2obb(const float* boxes, int n, int stride, float* out, jdet_stream_t stream);
 
 /* MaxIoUAssigner.assign_wrt_overlaps (models/boxes/assigner.py:L160-219) in two launches, no host
  * sync (the reference loops over gts in Python with a masked store per gt and jt.sync_all()).

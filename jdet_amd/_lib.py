@@ -31,6 +31,17 @@ class BnSumsJob(ctypes.Structure):          # jdet_bn_sums_job_t
     _fields_ = [("partial", _p), ("rows", _l), ("C", _i), ("gamma", _p), ("grad_gamma", _p), ("grad_beta", _p)]
 
 
+class GaussianLossParams(ctypes.Structure):  # jdet_gaussian_loss_params_t
+    _fields_ = [("kind", _i), ("fun", _i), ("tau", _f), ("alpha", _f), ("normalize", _i), ("sqrt_dist", _i),
+                ("beta", _f), ("eps", _f), ("decode_pred", _i), ("decode_target", _i), ("means", _f * 5),
+                ("stds", _f * 5), ("wh_ratio_clip", _f)]
+
+
+# jdet_gaussian_loss_params_t kinds / post-processing functions (include/jdet_hip.h)
+GD_KINDS = {"gwd": 0, "kld": 1, "jd": 2, "kld_symmax": 3, "kld_symmin": 4, "gwd_v1": 5, "kld_v1": 6, "bcd_v1": 7,
+            "kfiou": 8}
+GD_FUNS = {"none": 0, "": 0, None: 0, "log1p": 1, "sqrt": 2, "ln": 3, "exp": 4}
+
 EPI_FORWARD, EPI_ADD, EPI_MASK = 0, 1, 2
 
 # name -> (restype, argtypes); mirrors include/jdet_hip.h one to one (tests/test_abi.py checks it)
@@ -104,6 +115,8 @@ SIGNATURES = {
     "jdet_sigmoid_focal_loss_level": (_i, [_p, _p, _l, _l, _p, _l, _l, _l, _i, _f, _f, _p, _f, _p, _p, _p, _sz, _p]),
     "jdet_smooth_l1_loss_level": (_i, [_p, _p, _l, _l, _p, _l, _l, _l, _i, _f, _p, _f, _p, _p, _p, _sz, _p]),
     "jdet_loss_grad_scale": (_i, [_p, _l, _p, _p, _f, _p, _p]),
+    "jdet_gaussian_loss_level": (_i, [_p, _p, _l, _l, _p, _l, _l, _p, _l, _l, ctypes.POINTER(GaussianLossParams), _p, _f,
+                                      _p, _p, _p, _sz, _p]),
     "jdet_level_pack_nhwc": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p]),
     "jdet_align_conv_offset": (_i, [_p, _i, _i, _i, _f, _i, _p, _p]),
     "jdet_frozen_bn_act_forward": (_i, [_p, _p, _l, _i, _p, _p, _p, _p, _f, _i, _p, _p]),
@@ -125,6 +138,8 @@ SIGNATURES = {
     "jdet_oriented_delta_decode": (_i, [_p, _p, _l, _i, _p, _p, _f, _p, _p]),
     "jdet_oriented_delta_encode": (_i, [_p, _p, _l, _p, _p, _p, _p]),
     "jdet_anchor_targets_rotated": (_i, [_p, _p, _p, _p, _i, _i, _p, _p, _f, _p, _p, _p, _p, _p, _p]),
+    "jdet_anchor_targets_rotated_boxes": (_i, [_p, _p, _p, _i, _i, _f, _p, _p, _p, _p, _p, _p]),
+    "jdet_obb2hbb2obb": (_i, [_p, _i, _i, _p, _p]),
     "jdet_assign_max_iou_workspace": (_sz, [_i]),
     "jdet_assign_max_iou": (_i, [_p, _i, _i, _f, _f, _f, _f, _i, _i, _p, _i, _p, _p, _p, _p, _sz, _p]),
 }

@@ -108,3 +108,43 @@ def roitrans_train_cfg(backbone="Resnet50"):
                                grad_clip=dict(max_norm=35, norm_type=2)),
                 scheduler=dict(type="StepLR", warmup="linear", warmup_iters=500, warmup_ratio=1.0 / 3,
                                milestones=[8, 11]))
+
+
+def _gaussian_retinanet_cfg(head_type, loss_bbox, reg_decoded_bbox):
+    return dict(
+        model=dict(
+            type="RotatedRetinaNet",
+            backbone=dict(type="Resnet50", frozen_stages=1, return_stages=["layer1", "layer2", "layer3", "layer4"],
+                          pretrained=True),
+            neck=dict(type="FPN", in_channels=[256, 512, 1024, 2048], out_channels=256, start_level=1,
+                      add_extra_convs="on_input", num_outs=5),
+            bbox_head=dict(
+                type=head_type, num_classes=16, in_channels=256, feat_channels=256, stacked_convs=4,
+                octave_base_scale=4, scales_per_octave=3, anchor_ratios=[1.0, 0.5, 2.0],
+                anchor_strides=[8, 16, 32, 64, 128], target_means=[.0, .0, .0, .0, .0],
+                target_stds=[1.0, 1.0, 1.0, 1.0, 1.0],
+                loss_cls=dict(type="FocalLoss", use_sigmoid=True, gamma=2.0, alpha=0.25, loss_weight=1.0),
+                loss_bbox=loss_bbox,
+                test_cfg=dict(nms_pre=2000, min_bbox_size=0, score_thr=0.05, nms=dict(type="nms_rotated", iou_thr=0.1),
+                              max_per_img=2000),
+                train_cfg=dict(
+                    assigner=dict(type="MaxIoUAssigner", pos_iou_thr=0.5, neg_iou_thr=0.4, min_pos_iou=0,
+                                  ignore_iof_thr=-1, iou_calculator=dict(type="FakeBboxOverlaps2D_rotated")),
+                    bbox_coder=dict(type="DeltaXYWHABBoxCoder", target_means=(0., 0., 0., 0., 0.),
+                                    target_stds=(1., 1., 1., 1., 1.), clip_border=True),
+                    reg_decoded_bbox=reg_decoded_bbox, allowed_border=-1, pos_weight=-1, debug=False))),
+        **_SGD_1X)
+
+
+# The RotatedRetinaNet variants that swap the box loss for a Gaussian one (model section L1-61, optimizer and scheduler
+# from L132 on, of each file; tests/golden/configs/ holds them as `Config` reads them):
+# projects/rotated_retinanet_gwd/configs/rotated_retinanet_hbb_gwd_r50_fpn_1x_dota.py (L34-37: GDLoss gwd, L56 decoded)
+GWD_RETINANET_CFG = _gaussian_retinanet_cfg(
+    "RotatedRetinaHead", dict(type="GDLoss", loss_type="gwd", loss_weight=5.0), True)
+# projects/rotated_retinanet_kld/configs/rotated_retinanet_hbb_kld_r50_fpn_1x_dota.py (L34-39: GDLoss_v1 kld, L58 decoded)
+KLD_RETINANET_CFG = _gaussian_retinanet_cfg(
+    "RotatedRetinaHead", dict(type="GDLoss_v1", loss_type="kld", fun="log1p", tau=1.0, loss_weight=5.5), True)
+# projects/rotated_retinanet_kfiou/configs/rotated_retinanet_hbb_kfiou_r50_fpn_1x_dota.py (L17 KFIoURRetinaHead,
+# L34-36 KFLoss, L55 delta targets)
+KFIOU_RETINANET_CFG = _gaussian_retinanet_cfg(
+    "KFIoURRetinaHead", dict(type="KFLoss", loss_weight=5.0), False)

@@ -14,21 +14,9 @@
 //     kernel 2 owns one anchor per lane: column argmax (first maximum), neg / pos thresholds, the
 //     low-quality pass as "last gt i with overlaps[i,j] == gt_max[i] >= min_pos_iou wins"
 //     (equivalent to the reference's in-order overwrite loop), label gather.  No host sync.
-#include "common.h"
+#include "box_codec.h"
 
 namespace {
-
-// floor-mod norm_angle: (a + pi/4) mod pi - pi/4   (box_ops.py:L176-178, range [-pi/4, pi])
-__device__ __forceinline__ float norm_angle(float a) {
-  const float lo = (float)(-M_PI / 4), span = (float)M_PI;
-  const float x = a - lo;
-  float r = x - floorf(x / span) * span;  // python-style % for a positive modulus
-  return r + lo;
-}
-
-struct Vec5 {
-  float v[5];
-};
 
 __global__ __launch_bounds__(256) void delta2bbox_rotated_kernel(const float* __restrict__ rois,
                                                                  const float* __restrict__ deltas, long n,
@@ -36,23 +24,8 @@ __global__ __launch_bounds__(256) void delta2bbox_rotated_kernel(const float* __
                                                                  float max_ratio, float* __restrict__ out) {
   for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < n * ncls; idx += (long)gridDim.x * 256) {
     const long i = idx / ncls;
-    const float* r = rois + i * 5;
-    const float* d = deltas + idx * 5;
-    const float dx = d[0] * stds.v[0] + means.v[0];
-    const float dy = d[1] * stds.v[1] + means.v[1];
-    float dw = d[2] * stds.v[2] + means.v[2];
-    float dh = d[3] * stds.v[3] + means.v[3];
-    const float da = d[4] * stds.v[4] + means.v[4];
-    dw = fminf(fmaxf(dw, -max_ratio), max_ratio);
-    dh = fminf(fmaxf(dh, -max_ratio), max_ratio);
-    const float rx = r[0], ry = r[1], rw = r[2], rh = r[3], ra = r[4];
-    const float c = cosf(ra), s = sinf(ra);
-    float* o = out + idx * 5;
-    o[0] = dx * rw * c - dy * rh * s + rx;
-    o[1] = dx * rw * s + dy * rh * c + ry;
-    o[2] = rw * expf(dw);
-    o[3] = rh * expf(dh);
-    o[4] = norm_angle((float)M_PI * da + ra);
+    // box_codec.h: the arithmetic the Gaussian losses decode with, too
+    delta2bbox_one<float>(rois + i * 5, deltas + idx * 5, means, stds, max_ratio, out + idx * 5);
   }
 }
 
@@ -85,6 +58,8 @@ __global__ __launch_bounds__(256) void bbox2delta_rotated_kernel(const float* __
 // the pos_inds / neg_inds index lists: every anchor writes its own label, label weight, encoded box
 // target and box weight from its assignment (0 = negative, -1 = ignored, i+1 = gt i).  Fixed shapes
 // in and out -- no nonzero(), no host sync; the number of positives stays on the device.
+// kBoxes: `reg_decoded_bbox=True` (anchor_target.py:L79-80): the target is the assigned gt box itself, copied.
+template <bool kBoxes>
 __global__ __launch_bounds__(256) void anchor_targets_rotated_kernel(
     const float* __restrict__ anchors, const float* __restrict__ gt, const int32_t* __restrict__ gt_labels,
     const int32_t* __restrict__ gt_inds, int A, Vec5 means, Vec5 stds, float pos_weight,
@@ -97,7 +72,12 @@ __global__ __launch_bounds__(256) void anchor_targets_rotated_kernel(
     float* t = bbox_targets + (size_t)j * 5;
     float* w = bbox_weights + (size_t)j * 5;
     if (pos) {
-      encode_one(anchors + (size_t)j * 5, gt + (size_t)(gi - 1) * 5, means, stds, t);
+      if (kBoxes) {
+#pragma unroll
+        for (int k = 0; k < 5; k++) t[k] = gt[(size_t)(gi - 1) * 5 + k];
+      } else {
+        encode_one(anchors + (size_t)j * 5, gt + (size_t)(gi - 1) * 5, means, stds, t);
+      }
 #pragma unroll
       for (int k = 0; k < 5; k++) w[k] = 1.f;
       labels[j] = gt_labels ? gt_labels[gi - 1] : 1;
@@ -233,6 +213,31 @@ __global__ __launch_bounds__(256) void assign_row_argmax_apply_kernel(
   }
 }
 
+// FakeBboxOverlaps2D_rotated's box conversion (iou_calculator.py:L108-110 of the reference): hbb2obb(obb2hbb(b)),
+// ops/bbox_transforms.py:L639-645 and L653-665 there -- the enclosing horizontal box as an OBB, (w, h, 0) when
+// w >= h, else (h, w, -pi/2).  Same operations in the same order as the tensor program (whose flag blend
+// `flag * a + (1 - flag) * b` is a select up to the sign of a zero).
+__global__ __launch_bounds__(256) void obb2hbb2obb_kernel(const float* __restrict__ boxes, int n, int stride,
+                                                          float* __restrict__ out) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const float* b = boxes + (size_t)i * stride;
+  const float x = b[0], y = b[1], w = b[2], h = b[3], t = b[4];
+  const float c = cosf(t), s = sinf(t);
+  const float x_bias = fabsf(w / 2.f * c) + fabsf(h / 2.f * s);
+  const float y_bias = fabsf(w / 2.f * s) + fabsf(h / 2.f * c);
+  const float x1 = x - x_bias, y1 = y - y_bias, x2 = x + x_bias, y2 = y + y_bias;
+  const float cx = (x1 + x2) * 0.5f, cy = (y1 + y2) * 0.5f;
+  const float ww = x2 - x1, hh = y2 - y1;
+  const bool flag = ww >= hh;
+  float* o = out + (size_t)i * 5;
+  o[0] = cx;
+  o[1] = cy;
+  o[2] = flag ? ww : hh;
+  o[3] = flag ? hh : ww;
+  o[4] = flag ? 0.f : 0.f - (float)(M_PI / 2);
+}
+
 inline int grid_for(long n) {
   long g = (n + 255) / 256;
   return (int)(g > 262144 ? 262144 : (g < 1 ? 1 : g));
@@ -287,9 +292,33 @@ JDET_API int jdet_anchor_targets_rotated(const float* anchors, const float* gt, 
     m.v[k] = means5[k];
     s.v[k] = stds5[k];
   }
-  hipLaunchKernelGGL(anchor_targets_rotated_kernel, dim3((A + 255) / 256), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(anchor_targets_rotated_kernel<false>, dim3((A + 255) / 256), dim3(256), 0, (hipStream_t)stream,
                      anchors, gt, gt_labels, gt_inds, A, m, s, pos_weight, labels, label_weights, bbox_targets,
                      bbox_weights, num_pos);
+  return jdet_launch_status();
+}
+
+JDET_API int jdet_anchor_targets_rotated_boxes(const float* gt, const int32_t* gt_labels, const int32_t* gt_inds,
+                                               int A, int K, float pos_weight, int32_t* labels, float* label_weights,
+                                               float* bbox_targets, float* bbox_weights, int32_t* num_pos,
+                                               jdet_stream_t stream) {
+  if (A < 0 || K < 0) return JDET_E_BADARG;
+  if (A == 0) return JDET_OK;
+  if (!gt_inds || !labels || !label_weights || !bbox_targets || !bbox_weights || !num_pos || (K > 0 && !gt))
+    return JDET_E_BADARG;
+  const Vec5 unused = {{0.f, 0.f, 0.f, 0.f, 0.f}};
+  hipLaunchKernelGGL(anchor_targets_rotated_kernel<true>, dim3((A + 255) / 256), dim3(256), 0, (hipStream_t)stream,
+                     nullptr, gt, gt_labels, gt_inds, A, unused, unused, pos_weight, labels, label_weights,
+                     bbox_targets, bbox_weights, num_pos);
+  return jdet_launch_status();
+}
+
+JDET_API int jdet_obb2hbb2obb(const float* boxes, int n, int stride, float* out, jdet_stream_t stream) {
+  if (n < 0) return JDET_E_BADARG;
+  if (n == 0) return JDET_OK;   // an empty set, of any width (the calculator accepts (0, 0) boxes)
+  if (stride < 5 || !boxes || !out) return JDET_E_BADARG;
+  hipLaunchKernelGGL(obb2hbb2obb_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, boxes, n, stride,
+                     out);
   return jdet_launch_status();
 }
 

@@ -100,8 +100,9 @@ def anchor_target_single(flat_anchors, valid_flags, gt_bboxes, gt_bboxes_ignore,
 
 def _dense_ok(cfg, sampling, img_metas, gt_bboxes_ignore_list, anchors, encode_fn):
     """the case every single-stage rotated config hits: PseudoSampler, every anchor valid, no ignore
-    regions, MaxIoUAssigner on 5-parameter boxes, DeltaXYWHABBoxCoder targets, device tensors"""
-    if sampling or encode_fn is not None or cfg.get("reg_decoded_bbox", False) or cfg.get("allowed_border", -1) >= 0:
+    regions, MaxIoUAssigner on 5-parameter boxes, DeltaXYWHABBoxCoder targets (or the gt boxes themselves with
+    `reg_decoded_bbox`), device tensors"""
+    if sampling or encode_fn is not None or cfg.get("allowed_border", -1) >= 0:
         return False
     if not all(bool(m.get("_all_valid", False)) for m in img_metas):
         return False
@@ -133,10 +134,17 @@ def anchor_target_dense(anchor_list, gt_bboxes_list, gt_labels_list, cfg):
     bbox_weights = torch.empty((num_imgs, A, 5), dtype=torch.float32, device=dev)
     num_pos = torch.zeros((num_imgs,), dtype=torch.int32, device=dev)
     means, stds = L.vec5(coder.means), L.vec5(coder.stds)
+    decoded = cfg.get("reg_decoded_bbox", False)
     for i in range(num_imgs):
         anchors, gt = L.f32c(anchor_list[i]), L.f32c(gt_bboxes_list[i])
         res = assigner.assign(anchors, gt, None, None)
         gl = gt_labels_list[i].to(torch.int32).contiguous() if gt_labels_list[i] is not None else None
+        if decoded:     # the assigned gt boxes themselves (anchor_target.py:L79-80), copied in the same launch
+            L.check(L.lib().jdet_anchor_targets_rotated_boxes(
+                L.ptr(gt), L.ptr(gl), L.ptr(res.gt_inds), A, gt.shape[0], pos_weight, L.ptr(labels[i]),
+                L.ptr(label_weights[i]), L.ptr(bbox_targets[i]), L.ptr(bbox_weights[i]), L.ptr(num_pos[i:i + 1]),
+                L.stream_ptr(anchors)), "jdet_anchor_targets_rotated_boxes")
+            continue
         L.check(L.lib().jdet_anchor_targets_rotated(
             L.ptr(anchors), L.ptr(gt), L.ptr(gl), L.ptr(res.gt_inds), A, gt.shape[0], means, stds, pos_weight,
             L.ptr(labels[i]), L.ptr(label_weights[i]), L.ptr(bbox_targets[i]), L.ptr(bbox_weights[i]),

@@ -38,6 +38,42 @@ class BboxOverlaps2D_rotated_v1(_RotatedOverlaps):
     version = 1
 
 
+def fake_rotated_boxes(boxes):
+    """hbb2obb(obb2hbb(boxes)) (ops/bbox_transforms.py:L639-665 of the reference): the enclosing horizontal box as an
+    OBB.  Device tensors: ONE launch (jdet_obb2hbb2obb), the same operations in the same order as the tensor program;
+    host tensors: that program."""
+    import torch
+    from jdet_amd import _lib as L
+    if not boxes.is_cuda:
+        from jdet_amd.ops.bbox_transforms import hbb2obb, obb2hbb
+        return hbb2obb(obb2hbb(boxes))
+    b = L.f32c(boxes)
+    out = torch.empty((b.shape[0], 5), dtype=torch.float32, device=b.device)
+    L.check(L.lib().jdet_obb2hbb2obb(L.ptr(b), b.shape[0], b.shape[1], L.ptr(out), L.stream_ptr(b)), "jdet_obb2hbb2obb")
+    return out
+
+
+@BOXES.register_module()
+class FakeBboxOverlaps2D_rotated:
+    """IoU of the minimum enclosing horizontal boxes of two sets of rotated boxes, as rotated boxes
+    (iou_calculator.py:L81-119 of the reference): the conversion above, then box_iou_rotated."""
+
+    def __call__(self, bboxes1, bboxes2, mode="iou", is_aligned=False):
+        assert bboxes1.size(-1) in [0, 5, 6]
+        assert bboxes2.size(-1) in [0, 5, 6]
+        if bboxes2.size(-1) == 6:
+            bboxes2 = bboxes2[..., :5]
+        if bboxes1.size(-1) == 6:
+            bboxes1 = bboxes1[..., :5]
+        bboxes1 = fake_rotated_boxes(bboxes1)
+        bboxes2 = fake_rotated_boxes(bboxes2)
+        assert mode == "iou" and is_aligned is False
+        return bbox_overlaps_rotated(bboxes1, bboxes2)
+
+    def __repr__(self):
+        return self.__class__.__name__ + "()"
+
+
 def bbox_overlaps(bboxes1, bboxes2, mode="iou", is_aligned=False, eps=1e-6, version=0):
     """Axis-aligned overlaps, <x1,y1,x2,y2>; `version=1` is the legacy +1 pixel convention.
     Mirrors iou_calculator.py:L235-350 (elementwise tensor program -> torch)."""

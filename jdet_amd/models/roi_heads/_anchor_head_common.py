@@ -60,6 +60,15 @@ class RotatedAnchorHeadMixin:
             label_weights = label_weights.reshape(-1)
         cls_score = cls_score.permute(0, 2, 3, 1).reshape(-1, self.cls_out_channels)
         loss_cls = loss_cls_fn(cls_score, labels, label_weights, avg_factor=num_total_samples)
+        from jdet_amd.models.losses.gaussian_dist_loss import GaussianBoxLoss
+        if isinstance(loss_bbox_fn, GaussianBoxLoss):
+            # GDLoss / GDLoss_v1 / KFLoss: the deltas, the level's anchors and the target / weight windows go to ONE node
+            # per level that decodes in registers (losses/gaussian_dist_loss.py: GaussianBoxLoss.level) -- no torch
+            # decode, no flattening copies, no compaction by mask
+            bbox_pred = bbox_pred.permute(0, 2, 3, 1).reshape(-1, 5)
+            loss_bbox = loss_bbox_fn.level(bbox_pred, anchors, bbox_targets, bbox_weights, num_total_samples,
+                                           self._bbox_coder(cfg), cfg.get("reg_decoded_bbox", False))
+            return loss_cls, loss_bbox
         if not isinstance(loss_bbox_fn, (SmoothL1Loss, L1Loss)) or cfg.get("reg_decoded_bbox", False):
             bbox_targets = bbox_targets.reshape(-1, 5)
             bbox_weights = bbox_weights.reshape(-1, 5)
@@ -72,6 +81,12 @@ class RotatedAnchorHeadMixin:
             bbox_pred = bbox_coder.decode(anchors.reshape(-1, 5), bbox_pred)
         loss_bbox = loss_bbox_fn(bbox_pred, bbox_targets, bbox_weights, avg_factor=num_total_samples)
         return loss_cls, loss_bbox
+
+    def _bbox_coder(self, cfg):
+        bbox_coder_cfg = cfg.get("bbox_coder", "")
+        if bbox_coder_cfg == "":
+            bbox_coder_cfg = dict(type="DeltaXYWHBBoxCoder")
+        return build_from_cfg(bbox_coder_cfg, BOXES)
 
     def get_bboxes_single(self, cls_score_list, bbox_pred_list, mlvl_anchors, img_shape, scale_factor, cfg,
                           rescale=False):
