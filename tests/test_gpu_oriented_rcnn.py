@@ -48,6 +48,18 @@ def test_oriented_extractor_vs_per_level_oracle(dev, reference_order):
         m = lvl == i
         gref = O.roi_align_backward(O.V_ROT_V1, g[m], r2[m], feats_np[i].shape, 1.0 / s, 2) if m.any() else 0 * feats_np[i]
         np.testing.assert_allclose(feats[i].grad.cpu().contiguous().numpy(), gref, atol=3e-5)
+    # the path training takes: a channels-last gradient goes to the planned gather of every level (the contiguous one
+    # above falls through to jdet_roi_align_backward)
+    from jdet_amd.ops import _roi_common as RC
+    feats2 = [torch.from_numpy(f).to(dev).requires_grad_(True) for f in feats_np]
+    out2 = ext(feats2, torch.from_numpy(rois).to(dev))
+    assert all(isinstance(p, RC.BackwardPlan) for p in out2.grad_fn.plans)
+    np.testing.assert_array_equal(out2.detach().cpu().numpy(), ref)
+    out2.backward(torch.from_numpy(g).to(dev).contiguous(memory_format=torch.channels_last))
+    for i, s in enumerate(strides):
+        m = lvl == i
+        gref = O.roi_align_backward(O.V_ROT_V1, g[m], r2[m], feats_np[i].shape, 1.0 / s, 2) if m.any() else 0 * feats_np[i]
+        np.testing.assert_allclose(feats2[i].grad.cpu().contiguous().numpy(), gref, atol=3e-5)
     # the other two extractors resolve their layer class on the right ops module and route the same way
     e2 = RboxSingleRoIExtractor(dict(type="ROIAlignRotated", output_size=7, sampling_ratio=2), 8, strides).to(dev)
     o2 = e2([f.detach() for f in feats], torch.from_numpy(rois).to(dev)).cpu().numpy()
