@@ -34,16 +34,29 @@ int jdet_roi_align_forward_pool(int variant, const float* feat_nhwc, int N, int 
                                 const float* rois, int R, int PH, int PW, float spatial_scale, int sample_num,
                                 float* out_cl, void* workspace, size_t workspace_bytes, jdet_stream_t stream);
 
-/* The two measured alternatives of the RoIAlign forward that shipped inside libjdet_hip.so behind a process-wide mode in
- * round 4 (csrc/experimental/roi_align_modes.hip compiles the product's kernels file with them), channels-last result:
+/* The measurement side of the RoIAlign forward (csrc/experimental/roi_align_modes.hip: the product's forward header
+ * csrc/roi_align_fwd.h plus the measured alternatives and the profiling builds of the product kernels), channels-last
+ * result.  Except for mode 2, `order` is a schedule of jdet_roi_spatial_order or NULL, the workspace is unused, and the
+ * product kernels run wherever a mode does not apply to a shape.
+ *   mode 0: the product arithmetic launched from this library, with the profiling builds of the merged-tap kernel
+ *           selectable from the environment (read once per process): JDET_ROI_FWD_GRAN = 2 / 1 rows per guarded group of
+ *           the per-bin loop, 128 / 384 workgroup time stamps into the output rows (per-bin loop / rolling window), 768
+ *           prologue only; JDET_ROI_FWD_LDS_KB the LDS request (workgroups per CU).
  *   mode 2: the merged-tap arithmetic through the CHANNEL-SLICED kernels (roi_align_sliced.h): one launch sorts the RoIs
  *           by the Morton code of their centre and writes the PLAN (per (RoI, bin) the merged tap list), the second
  *           gives every XCD one 32-channel slice of every RoI.  sample_num == 2, PH*PW >= 16, C % 32 == 0; bit-equal
  *           to jdet_roi_align_forward_cl.  `order` unused.  workspace: schedule + plan (~136 bytes per (RoI, bin)).
  *   mode 3: every distinct pixel row of a LINE of bins loaded once (roi_align_line.h); sample_num == 2, PH, PW <= 8
- *           (elsewhere the product kernels run); values as the product's up to the order of a bin's sum.  `order`: a
- *           schedule of jdet_roi_spatial_order or NULL; workspace unused.
- * Both measured slower than the product kernel at the north-star point (profiles/r04_roi_fwd_notes.md). */
+ *           (elsewhere the product kernels run); values as the product's up to the order of a bin's sum.
+ *   mode 4: the footprint-staged kernel (roi_align_stage.h): distinct pixels of a line of bins fetched once by LDS-DMA;
+ *           sample_num == 2, PH, PW <= 8, C % 64 == 0, no orientation planes; values as mode 3's.  JDET_ROI_STAGE_CPP /
+ *           JDET_ROI_STAGE_ABL: channels per pass, ablations (profiling).
+ *   mode 5: taps merged over PAIRS of neighbouring bins (roi_align_pair.h); sample_num == 2, PH*PW <= 64; values as
+ *           mode 3's.
+ *   mode 6: the per-bin tap loop of the merged-tap kernel, which the product's rolling window replaced: bit-equal to
+ *           jdet_roi_align_forward_cl under the same `order` (tests/test_gpu_roi_align_ring.py).
+ * Any other mode: JDET_E_BADARG.  Modes 2-5 measured slower than the product kernel at the north-star point
+ * (profiles/r04_roi_fwd_notes.md, r06_roi_fwd_staged.md, r06_roi_fwd_ring.md). */
 size_t jdet_roi_align_forward_cl_mode_workspace(int mode, int R, int PH, int PW);
 int jdet_roi_align_forward_cl_mode(int mode, int variant, const float* feat_nhwc, int N, int C, int H, int W,
                                    const float* rois, int R, int PH, int PW, float spatial_scale, int sample_num,

@@ -21,7 +21,7 @@
 // for the merged-tap kernel: the set-up (table init + hash inserts behind the double-precision trig: 11.7 us per
 // workgroup, every wave waiting) and 14 packed FMAs + 3 LDS reads per row cost more than the saved rows.  Forward
 // jdet_roi_align_forward_cl_mode(3, ...) of libjdet_experimental.so runs it; not a product path.
-// (Included by roi_align_impl.inc (JDET_ROI_EXPERIMENTAL_MODES) inside its unnamed namespace, after the merged-tap kernel.)
+// (Included by roi_align_modes.hip inside its unnamed namespace, after the product forward header ../roi_align_fwd.h.)
 #pragma once
 
 constexpr int kLineSlots = 128;          // >= 8 bins x 16 taps; a power of two (hash: 7 bits)

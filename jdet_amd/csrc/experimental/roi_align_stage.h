@@ -212,9 +212,9 @@ __global__ __launch_bounds__(kThreads) void roi_align_fwd_staged_kernel(
   __syncthreads();                                                                   // (A)
   if (__builtin_amdgcn_readfirstlane(*s_flag)) {
     // a line's tap box does not fit its bitmap (RoI sides beyond ~90 map pixels): direct path of the reference-order
-    // kernel (roi_align_impl.inc) for this RoI
+    // kernel (../roi_align_fwd.h) for this RoI
     for (int c0 = 0; c0 < C; c0 += kChunkC)
-      direct_chunk<VARIANT, 4, 4, 0, true, 0>(g, rsrc, c0, min(kChunkC, C - c0), C, H, W, PW, nbins, wave, lane, nullptr,
+      direct_chunk<VARIANT, 4, 4, true, 0>(g, rsrc, c0, min(kChunkC, C - c0), C, H, W, PW, nbins, wave, lane, nullptr,
                                               out + (size_t)r * nbins * C);
     return;
   }

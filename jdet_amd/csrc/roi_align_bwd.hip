@@ -234,12 +234,157 @@ int build_plan(const float* rois, int R, int N, int H, int W, int PH, int PW, fl
   return patch_finish(w, nkeys, R, seg_cap, st);
 }
 
-}  // namespace
+// ---- atomic-scatter backward (all dialects, any sampling): the path of the calls the gather does not take (adaptive
+// sampling, odd channel counts, no workspace).  grad_out chunk staged in LDS, samples broadcast from their lanes as in
+// the forward, hardware global_atomic_add_f32 into the NHWC gradient (lane-contiguous 256 B per instruction). ----
+template <int VARIANT>
+__global__ __launch_bounds__(kBlock) void roi_align_bwd_kernel(
+    const float* __restrict__ grad_out, const float* __restrict__ rois, float* __restrict__ grad_in,
+    int C, int H, int W, int PH, int PW, float spatial_scale, int sample_num, int nO,
+    const int32_t* __restrict__ order) {
+  extern __shared__ __attribute__((aligned(16))) float s_g[];  // [cc][nbins]
+  constexpr int ROI_COLS = (VARIANT == JDET_ROI_HBB_V0 || VARIANT == JDET_ROI_HBB_V1) ? 5 : 6;
+  constexpr int CHMAP = 1;
+  const int r = order ? order[blockIdx.x] : blockIdx.x;
+  const int c0 = blockIdx.y * kChunkC;
+  const int cc = min(kChunkC, C - c0);
+  const int nbins = PH * PW;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  if ((int)rois[(size_t)r * ROI_COLS] < 0) return;  // masked RoI (block-uniform, before any barrier)
 
-// Defined in roi_align.hip: the atomic scatter path (RiRoI, adaptive sampling, odd channel counts).
-int jdet_roi_align_backward_atomic(int variant, const float* grad_out, const float* rois, int R, int N, int C,
-                                   int H, int W, int PH, int PW, float spatial_scale, int sample_num,
-                                   int n_orient, const int32_t* order, float* grad_in, hipStream_t st);
+  // stage grad_out[r, c0:c0+cc, :, :] (contiguous) into LDS
+  {
+    const float* __restrict__ src = grad_out + ((size_t)r * C + c0) * nbins;
+    const int total = cc * nbins;
+    if (((total & 3) == 0) && ((((size_t)r * C + c0) * nbins) & 3) == 0) {
+      const float4* s4 = reinterpret_cast<const float4*>(src);
+      float4* d4 = reinterpret_cast<float4*>(s_g);
+      for (int i = threadIdx.x; i < (total >> 2); i += kBlock) d4[i] = s4[i];
+    } else {
+      for (int i = threadIdx.x; i < total; i += kBlock) s_g[i] = src[i];
+    }
+  }
+  __syncthreads();
+
+  const RoiGeom g = roi_geom<VARIANT>(rois + (size_t)r * ROI_COLS, spatial_scale, sample_num, PH,
+                                      PW, nO, true);
+  float* __restrict__ img = grad_in + (size_t)g.batch * H * W * C;
+
+  int dst0[4], dst1[4];
+  bool cval[4];
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const int cl = chan_of<CHMAP>(lane, k);
+    cval[k] = cl < cc;
+    const int ch = c0 + (cval[k] ? cl : 0);
+    if (VARIANT == JDET_ROI_RIROI) {
+      const int c = ch / nO, o = ch % nO;
+      const int ind_rot = (o - g.ind + nO) % nO;
+      const int ind_rot_plus = (ind_rot + 1 + nO) % nO;
+      dst0[k] = c * nO + ind_rot;
+      dst1[k] = c * nO + ind_rot_plus;
+    } else {
+      dst0[k] = ch;
+      dst1[k] = ch;
+    }
+  }
+
+  const int spb = g.grid_h * g.grid_w;
+  if (spb <= 0) return;  // count == 0: the reference divides by zero -> inf*0; nothing sane to add
+  const int nb = (nbins - wave + 3) >> 2;
+  const int bpc = spb <= 64 ? 64 / spb : 1;
+  const int passes = spb <= 64 ? 1 : (spb + 63) / 64;
+
+  auto lane_sample = [&](int kg, int pass) -> Sample {
+    int my_kb, my_r;
+    if (passes == 1) {
+      my_kb = lane / spb;
+      my_r = lane % spb;
+    } else {
+      my_kb = 0;
+      my_r = pass * 64 + lane;
+    }
+    const int my_bin = wave + 4 * (kg + my_kb);
+    const bool ok = my_kb < bpc && my_bin < nbins && my_r < spb;
+    const int iy = ok ? my_r / g.grid_w : 0;
+    const int ix = ok ? my_r % g.grid_w : 0;
+    const int bb = ok ? my_bin : 0;
+    Sample m = make_sample<VARIANT>(g, bb / PW, bb % PW, iy, ix, H, W);
+    // fold 1/count into the weights once per sample (reference: top*w/count per element)
+    m.w1 /= g.count;
+    m.w2 /= g.count;
+    m.w3 /= g.count;
+    m.w4 /= g.count;
+    return m;
+  };
+
+  for (int kg = 0; kg < nb; kg += bpc) {
+    Sample mine = lane_sample(kg, 0);
+    for (int kb = 0; kb < bpc && kg + kb < nb; kb++) {
+      const int bin = wave + 4 * (kg + kb);
+      float top[4];
+#pragma unroll
+      for (int k = 0; k < 4; k++) top[k] = cval[k] ? s_g[chan_of<CHMAP>(lane, k) * nbins + bin] : 0.f;
+      for (int pass = 0; pass < passes; pass++) {
+        if (passes > 1) mine = lane_sample(kg, pass);
+        const int lane0 = passes == 1 ? kb * spb : 0;
+        const int ns = passes == 1 ? spb : min(64, spb - pass * 64);
+        for (int j = 0; j < ns; j++) {
+          const Sample s = bcast(mine, lane0 + j);
+          if (!s.valid) continue;
+#pragma unroll
+          for (int k = 0; k < 4; k++) {
+            if (!cval[k]) continue;
+            const float g1 = top[k] * s.w1, g2 = top[k] * s.w2, g3 = top[k] * s.w3, g4 = top[k] * s.w4;
+            if (VARIANT == JDET_ROI_RIROI) {
+              unsafeAtomicAdd(img + (size_t)s.o1 * C + dst0[k], g1 * g.r_var);
+              unsafeAtomicAdd(img + (size_t)s.o2 * C + dst0[k], g2 * g.r_var);
+              unsafeAtomicAdd(img + (size_t)s.o3 * C + dst0[k], g3 * g.r_var);
+              unsafeAtomicAdd(img + (size_t)s.o4 * C + dst0[k], g4 * g.r_var);
+              unsafeAtomicAdd(img + (size_t)s.o1 * C + dst1[k], g1 * g.l_var);
+              unsafeAtomicAdd(img + (size_t)s.o2 * C + dst1[k], g2 * g.l_var);
+              unsafeAtomicAdd(img + (size_t)s.o3 * C + dst1[k], g3 * g.l_var);
+              unsafeAtomicAdd(img + (size_t)s.o4 * C + dst1[k], g4 * g.l_var);
+            } else {
+              unsafeAtomicAdd(img + (size_t)s.o1 * C + dst0[k], g1);
+              unsafeAtomicAdd(img + (size_t)s.o2 * C + dst0[k], g2);
+              unsafeAtomicAdd(img + (size_t)s.o3 * C + dst0[k], g3);
+              unsafeAtomicAdd(img + (size_t)s.o4 * C + dst0[k], g4);
+            }
+          }
+        }
+      }
+    }
+  }
+}
+
+template <int VARIANT>
+int launch_bwd(const float* gout, const float* rois, float* gin, int R, int C, int H, int W, int PH,
+               int PW, float scale, int sample_num, int nO, const int32_t* order, hipStream_t st) {
+  const int chunks = jdet_cdiv(C, kChunkC);
+  const size_t lds = (size_t)min(C, kChunkC) * PH * PW * sizeof(float);
+  hipLaunchKernelGGL((roi_align_bwd_kernel<VARIANT>), dim3(R, chunks), dim3(kBlock), lds, st, gout,
+                     rois, gin, C, H, W, PH, PW, scale, sample_num, nO, order);
+  return jdet_launch_status();
+}
+
+int backward_atomic(int variant, const float* grad_out, const float* rois, int R, int N, int C, int H, int W, int PH,
+                    int PW, float spatial_scale, int sample_num, int n_orient, const int32_t* order, float* grad_in,
+                    hipStream_t st) {
+  if (!grad_in && (long)N * C * H * W > 0) return JDET_E_BADARG;
+  int e = check_common(variant, grad_out, rois, grad_in, N, C, H, W, R, PH, PW, n_orient);
+  if (e) return e;
+  int he = jdet_zero_async(grad_in, sizeof(float) * (size_t)N * C * H * W, st);
+  if (he) return he;
+  if (R == 0) return JDET_OK;
+  return with_variant(variant, [&](auto v) {
+    constexpr int V = decltype(v)::value;
+    return launch_bwd<V>(grad_out, rois, grad_in, R, C, H, W, PH, PW, spatial_scale, sample_num,
+                         V == JDET_ROI_RIROI ? n_orient : 1, order, st);
+  });
+}
+
+}  // namespace
 
 static bool gather_ok(int variant, int R, int N, int C, int H, int W, int PH, int PW, int sample_num) {
   if (sample_num <= 0 || C % 4 != 0 || R <= 0) return false;
@@ -289,15 +434,15 @@ JDET_API int jdet_roi_align_backward(int variant, const float* grad_out, const f
   hipStream_t st = (hipStream_t)stream;
   const size_t need = jdet_roi_align_backward_workspace(variant, R, N, C, H, W, PH, PW, sample_num);
   if (need == 0 || workspace == nullptr)
-    return jdet_roi_align_backward_atomic(variant, grad_out, rois, R, N, C, H, W, PH, PW, spatial_scale,
-                                          sample_num, n_orient, order, grad_in, st);
+    return backward_atomic(variant, grad_out, rois, R, N, C, H, W, PH, PW, spatial_scale, sample_num, n_orient, order,
+                           grad_in, st);
   if (workspace_bytes < need) return JDET_E_WORKSPACE;
   if (variant < 0 || variant > 4 || N <= 0 || C <= 0 || H <= 0 || W <= 0 || PH <= 0 || PW <= 0 || !grad_out ||
       !rois || !grad_in)
     return JDET_E_BADARG;
   if (variant == JDET_ROI_RIROI && (n_orient < 1 || n_orient > 16 || C % n_orient != 0))
-    return jdet_roi_align_backward_atomic(variant, grad_out, rois, R, N, C, H, W, PH, PW, spatial_scale,
-                                          sample_num, n_orient, order, grad_in, st);
+    return backward_atomic(variant, grad_out, rois, R, N, C, H, W, PH, PW, spatial_scale, sample_num, n_orient, order,
+                           grad_in, st);
   return backward_gather(variant, grad_out, rois, R, N, C, H, W, PH, PW, spatial_scale, sample_num, grad_in,
                          workspace, false, false, st, n_orient);
 }

@@ -1,5 +1,9 @@
 // RoIAlign family for gfx950 (MI355X): ROIAlignRotated, ROIAlignRotated_v1, RiRoIAlign and the
-// horizontal ROIAlign v0/v1, forward and backward.
+// horizontal ROIAlign v0/v1 -- the PRODUCT forward: its three kernel families (merged taps, vector, scalar fallback)
+// and the launcher that picks among them.  roi_align.hip holds the entry points; the backward is roi_align_bwd.hip.
+// Everything that exists to be measured -- alternative kernels, profiling instantiations of the kernels below, the
+// environment knobs that select them -- lives in libjdet_experimental.so, whose RoIAlign translation unit includes this
+// header: nothing here reads the environment or compiles conditionally.
 //
 // Reference semantics (per output element, fp32):
 //   python/jdet/ops/roi_align_rotated.py:L21-127 (fwd), L128-255 (bwd)
@@ -21,10 +25,7 @@
 //     the CPU oracle.
 //   * results are staged in LDS as [channel][bin] and written out as one contiguous,
 //     float4-coalesced (C_chunk*PH*PW) block in the reference's (R,C,PH,PW) layout.
-//   * backward: grad_out chunk staged in LDS, same sample broadcast, hardware
-//     global_atomic_add_f32 into the NHWC gradient (lane-contiguous 256 B per instruction).
-#include <stdlib.h>
-
+#pragma once
 #include <type_traits>
 
 #include "roi_geom.h"
@@ -166,17 +167,11 @@ __device__ __forceinline__ void acc_sample(float (&acc)[4], const RoiGeom& g, in
   }
 }
 
-#ifdef JDET_ROI_EXPERIMENTAL_MODES
-#include "experimental/roi_align_sliced.h"   // channel-sliced forward (measured alternative: libjdet_experimental.so)
-#endif
-
 // ---- vector fast path: C % 4 == 0, map < 2 GiB per image; RiRoI with 4 or 8 orientation planes -------------
 // Lane owns 4 consecutive channels.  Taps are fetched with buffer_load_dwordx4 whose per-tap
 // pixel byte offset is an SGPR (soffset) -- no per-load 64-bit VALU address arithmetic -- and the
 // per-sample geometry is broadcast from the owning lane with v_readlane.
 //   NW  = waves per workgroup;  SG = samples whose 4*SG taps are all in flight before first use
-//   ABL = ablation switches for profiling builds only (0 in production):
-//         1 taps forced to pixels 0..3 (L1-resident), 2 no interpolation math, 4 no output stream
 // Per-RoI prologue shared by the vector kernels: geometry with the control-flow / addressing
 // scalars pinned into SGPRs (hipcc otherwise wraps every buffer_load in a waterfall loop, guide
 // T20), and a raw buffer descriptor over the RoI's image (out-of-range reads return 0).
@@ -204,7 +199,7 @@ __device__ __forceinline__ RoiGeom vec_prologue(const float* feat, const float* 
 // byte offset is an SGPR; results go to s_out[channel][bin].  NW waves split the bins.
 // OUT_CL: results go straight from registers to the channels-last output row (r, bin, c0 + 4*lane .. +3) -- one
 // contiguous 1 KiB non-temporal store per (wave, bin), no LDS staging; otherwise to s_out[channel][bin].
-template <int VARIANT, int NW, int SG, int ABL, bool OUT_CL = false, int NO = 0>
+template <int VARIANT, int NW, int SG, bool OUT_CL = false, int NO = 0>
 __device__ __forceinline__ void direct_chunk(const RoiGeom& g, const __amdgpu_buffer_rsrc_t rsrc, int c0,
                                              int cc, int C, int H, int W, int PW, int nbins, int wave,
                                              int lane, float* __restrict__ s_out, float* __restrict__ out_row = nullptr) {
@@ -232,7 +227,6 @@ __device__ __forceinline__ void direct_chunk(const RoiGeom& g, const __amdgpu_bu
     const int ix = ok ? my_r % g.grid_w : 0;
     const int bb = ok ? my_bin : 0;
     Sample s = make_sample<VARIANT>(g, bb / PW, bb % PW, iy, ix, H, W);
-    if (ABL & 1) { s.o1 = 0; s.o2 = 1; s.o3 = 2; s.o4 = 3; }
     s.o1 *= pix_bytes; s.o2 *= pix_bytes; s.o3 *= pix_bytes; s.o4 *= pix_bytes;
     return s;
   };
@@ -267,14 +261,9 @@ __device__ __forceinline__ void direct_chunk(const RoiGeom& g, const __amdgpu_bu
               t[u][2] = tap(sv[u].o3);
               t[u][3] = tap(sv[u].o4);
             }
-            if (ABL & 2) {
 #pragma unroll
-              for (int u = 0; u < SG; u++) acc[0] += t[u][0].x + t[u][1].y + t[u][2].z + t[u][3].w;
-            } else {
-#pragma unroll
-              for (int u = 0; u < SG; u++)
-                acc_sample<NO>(acc, g, lane, sv[u].w1, sv[u].w2, sv[u].w3, sv[u].w4, t[u][0], t[u][1], t[u][2], t[u][3]);
-            }
+            for (int u = 0; u < SG; u++)
+              acc_sample<NO>(acc, g, lane, sv[u].w1, sv[u].w2, sv[u].w3, sv[u].w4, t[u][0], t[u][1], t[u][2], t[u][3]);
           } else {
 #pragma unroll
             for (int u = 0; u < SG; u++)
@@ -302,7 +291,7 @@ __device__ __forceinline__ void direct_chunk(const RoiGeom& g, const __amdgpu_bu
   }
 }
 
-template <int VARIANT, int NW, int SG, int ABL, bool OUT_CL = false, int NO = 0>
+template <int VARIANT, int NW, int SG, bool OUT_CL = false, int NO = 0>
 __global__ __launch_bounds__(NW * 64) void roi_align_fwd_vec_kernel(
     const float* __restrict__ feat, const float* __restrict__ rois, float* __restrict__ out,
     int C, int H, int W, int PH, int PW, float spatial_scale, int sample_num,
@@ -320,17 +309,13 @@ __global__ __launch_bounds__(NW * 64) void roi_align_fwd_vec_kernel(
                                           NO ? NO : 1);
   if (g.batch < 0) return;  // masked RoI (belongs to another pyramid level): its output rows are not ours
   if (OUT_CL) {
-    direct_chunk<VARIANT, NW, SG, ABL, true, NO>(g, rsrc, c0, cc, C, H, W, PW, nbins, wave, lane, s_out,
+    direct_chunk<VARIANT, NW, SG, true, NO>(g, rsrc, c0, cc, C, H, W, PW, nbins, wave, lane, s_out,
                                                  out + (size_t)r * nbins * C);
     return;
   }
-  direct_chunk<VARIANT, NW, SG, ABL, false, NO>(g, rsrc, c0, cc, C, H, W, PW, nbins, wave, lane, s_out);
+  direct_chunk<VARIANT, NW, SG, false, NO>(g, rsrc, c0, cc, C, H, W, PW, nbins, wave, lane, s_out);
   __syncthreads();
   float* __restrict__ dst = out + ((size_t)r * C + c0) * nbins;
-  if (ABL & 4) {
-    if (threadIdx.x == 0) dst[0] = s_out[0];
-    return;
-  }
   // coalesced write-out of the contiguous [cc][nbins] block (cc % 4 == 0 -> 16 B aligned)
   const int total = cc * nbins;
   const float4* s4 = reinterpret_cast<const float4*>(s_out);
@@ -356,6 +341,10 @@ __global__ __launch_bounds__(NW * 64) void roi_align_fwd_vec_kernel(
 // The *_reference entry points select the reference-order kernel above (bit-identical to the oracle).
 // NO = 4 / 8: RiRoIAlign -- VARIANT is the rotated geometry, the orientation planes are mixed once per bin on the
 // finished sum (the reference mixes per sample: equal up to fp32 re-association, like the merged weights).
+// ABL = 0 (the per-bin tap loop) or 256 (the rolling window, channels-last output only) in this library.  The experimental
+// library instantiates the profiling builds: 32 / 64 rows requested in guarded groups of 2 / 1 (per-bin loop), 128
+// workgroup time stamps into the output rows, 512 prologue only (with 256).
+
 // profiling builds (ABL & 128): the 100 MHz wall clock read WHEN `dep` has been produced (the operand pins the order)
 __device__ __forceinline__ long long stamp_after(int dep) {
   unsigned long long t;
@@ -366,7 +355,7 @@ __device__ __forceinline__ long long stamp_after(int dep) {
 template <int VARIANT, int NW, int ABL = 0, bool OUT_CL = false, int NO = 0>
 __global__ __launch_bounds__(NW * 64) void roi_align_fwd_merged_kernel(
     const float* __restrict__ feat, const float* __restrict__ rois, float* __restrict__ out,
-    int C, int H, int W, int PH, int PW, float spatial_scale, const int32_t* __restrict__ order, int abl_mask) {
+    int C, int H, int W, int PH, int PW, float spatial_scale, const int32_t* __restrict__ order) {
   extern __shared__ __attribute__((aligned(16))) float s_out[];  // [cc][nbins]; first 2 KiB/wave: tap lists
   __shared__ float s_trig[2];
   long long stamp0 = 0;
@@ -381,13 +370,8 @@ __global__ __launch_bounds__(NW * 64) void roi_align_fwd_merged_kernel(
   constexpr bool kRot = ROI_COLS == 6;
   const float* roi = rois + (size_t)r * ROI_COLS;
   if (kRot && wave == 0 && lane == 0) {
-    if (ABL & 16) {   // profiling builds: how much of the workgroup's start-up is the double-precision trig
-      s_trig[0] = cosf(roi[5]);
-      s_trig[1] = sinf(roi[5]);
-    } else {
-      s_trig[0] = (float)cos((double)roi[5]);
-      s_trig[1] = (float)sin((double)roi[5]);
-    }
+    s_trig[0] = (float)cos((double)roi[5]);
+    s_trig[1] = (float)sin((double)roi[5]);
   }
   __amdgpu_buffer_rsrc_t rsrc;
   RoiGeom g = vec_prologue<VARIANT, false>(feat, rois, r, C, H, W, PH, PW, spatial_scale, 2, rsrc);
@@ -413,9 +397,6 @@ __global__ __launch_bounds__(NW * 64) void roi_align_fwd_merged_kernel(
   const int bb = bin_ok ? my_bin : 0;
   Sample s = make_sample<VARIANT>(g, bb / PW, bb % PW, q >> 1, q & 1, H, W);
   if (!bin_ok) s.valid = 0;
-  if (ABL & 1) {   // profiling builds: same tap structure, every tap inside one (abl_mask+1)-pixel window
-    s.o1 &= abl_mask; s.o2 &= abl_mask; s.o3 &= abl_mask; s.o4 &= abl_mask;
-  }
   const int o[4] = {s.o1 * pix_bytes, s.o2 * pix_bytes, s.o3 * pix_bytes, s.o4 * pix_bytes};
   if (ABL & 128) st_c = stamp_after(o[0] + o[3]);                   // sample geometry
   const float w[4] = {s.w1, s.w2, s.w3, s.w4};
@@ -768,35 +749,14 @@ __global__ __launch_bounds__(NW * 64) void roi_align_fwd_merged_kernel(
   }
   __syncthreads();
   float* __restrict__ dst = out + ((size_t)r * C + c0) * nbins;
-  if (ABL & 4) {
-    if (threadIdx.x == 0) dst[0] = s_out[0];
-    return;
-  }
   const int total = cc * nbins;
-  const float4* s4 = reinterpret_cast<const float4*>(s_out);
-  float4* d4 = reinterpret_cast<float4*>(dst);
-  if (ABL & 8) {
-    for (int i = threadIdx.x; i < (total >> 2); i += NW * 64) d4[i] = s4[i];
-  } else {
-    // write-once output: non-temporal stores keep the 100 MB result stream from evicting map lines out of L2
-    // (67.5 -> 64.6 us/step)
-    typedef float v4s __attribute__((ext_vector_type(4)));
-    const v4s* sv = reinterpret_cast<const v4s*>(s_out);
-    v4s* dv = reinterpret_cast<v4s*>(dst);
-    for (int i = threadIdx.x; i < (total >> 2); i += NW * 64) __builtin_nontemporal_store(sv[i], &dv[i]);
-  }
+  // write-once output: non-temporal stores keep the 100 MB result stream from evicting map lines out of L2
+  // (67.5 -> 64.6 us/step)
+  typedef float v4s __attribute__((ext_vector_type(4)));
+  const v4s* sv = reinterpret_cast<const v4s*>(s_out);
+  v4s* dv = reinterpret_cast<v4s*>(dst);
+  for (int i = threadIdx.x; i < (total >> 2); i += NW * 64) __builtin_nontemporal_store(sv[i], &dv[i]);
 }
-
-#ifdef JDET_ROI_EXPERIMENTAL_MODES
-#include "experimental/roi_align_line.h"     // taps deduplicated over a line of bins (measured alternative)
-#include "experimental/roi_align_pair.h"     // taps merged over PAIRS of neighbouring bins (round 6, measured alternative)
-#endif
-
-}  // namespace
-// (outside the anonymous namespace: the launcher takes the kernel's address for hipFuncSetAttribute, and hipcc does not
-//  emit the host-side handle of an internal-linkage kernel template whose address is taken)
-#include "roi_align_stage.h"                 // footprint-staged forward: distinct pixels of a line by LDS-DMA (round 6)
-namespace {
 
 // (An LDS pixel-cache variant -- per-RoI bitmap + rank dedup, distinct pixels staged once per 64-channel pass, taps
 // served by ds_read_b128 -- was built and measured at 155 us against 69 us for the direct path at the time: four
@@ -914,582 +874,75 @@ __global__ __launch_bounds__(kBlock) void roi_align_fwd_kernel(
 }
 
 // ---------------------------------------------------------------------------------------------
-// Backward (feature gradient)
+// Launcher
 // ---------------------------------------------------------------------------------------------
-template <int VARIANT>
-__global__ __launch_bounds__(kBlock) void roi_align_bwd_kernel(
-    const float* __restrict__ grad_out, const float* __restrict__ rois, float* __restrict__ grad_in,
-    int C, int H, int W, int PH, int PW, float spatial_scale, int sample_num, int nO,
-    const int32_t* __restrict__ order) {
-  extern __shared__ __attribute__((aligned(16))) float s_g[];  // [cc][nbins]
-  constexpr int ROI_COLS = (VARIANT == JDET_ROI_HBB_V0 || VARIANT == JDET_ROI_HBB_V1) ? 5 : 6;
-  constexpr int CHMAP = 1;
-  const int r = order ? order[blockIdx.x] : blockIdx.x;
-  const int c0 = blockIdx.y * kChunkC;
-  const int cc = min(kChunkC, C - c0);
-  const int nbins = PH * PW;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  if ((int)rois[(size_t)r * ROI_COLS] < 0) return;  // masked RoI (block-uniform, before any barrier)
+// Arithmetic of a forward call (an argument of the launcher, chosen by the ENTRY POINT -- there is no process-wide
+// mode): merged taps (the product entry points) or the reference's operation order (the *_reference entry points:
+// bit-identical to the CPU oracle, the parity twin).
+constexpr int kFwdMerged = 0, kFwdReference = 1;
 
-  // stage grad_out[r, c0:c0+cc, :, :] (contiguous) into LDS
-  {
-    const float* __restrict__ src = grad_out + ((size_t)r * C + c0) * nbins;
-    const int total = cc * nbins;
-    if (((total & 3) == 0) && ((((size_t)r * C + c0) * nbins) & 3) == 0) {
-      const float4* s4 = reinterpret_cast<const float4*>(src);
-      float4* d4 = reinterpret_cast<float4*>(s_g);
-      for (int i = threadIdx.x; i < (total >> 2); i += kBlock) d4[i] = s4[i];
-    } else {
-      for (int i = threadIdx.x; i < total; i += kBlock) s_g[i] = src[i];
-    }
-  }
-  __syncthreads();
+// Launch shape of the vector kernels: the winners of the tuning ladders of rounds 1-3 (2 / 4 / 8 / 16 waves per workgroup,
+// 2 / 4 / 8 samples in flight; profiles/r01_roi_align_fwd_ablations.txt).
+constexpr int kFwdWaves = 4, kFwdSG = 4;
+// The merged kernel keeps its per-wave tap lists in the first 2 KiB / wave of the dynamic LDS block (the request has
+// room for 8 waves).
+constexpr size_t kFwdListLds = 8 * 2048;
+// LDS request of the channels-last merged launch.  It caps the workgroups per CU at 4 (36 KiB each; the tap lists need
+// 16): one workgroup fewer in flight per CU leaves the time where it is (59.4 vs 60.9 us at the north-star point) and
+// cuts the reads beyond the L2 by 14 % (1.34 M vs 1.55 M 128-byte requests, profiles/r03_roi_pool_notes.md) -- fewer
+// RoIs in flight, smaller working set.
+constexpr size_t kFwdClLds = 36 * 1024;
 
-  const RoiGeom g = roi_geom<VARIANT>(rois + (size_t)r * ROI_COLS, spatial_scale, sample_num, PH,
-                                      PW, nO, true);
-  float* __restrict__ img = grad_in + (size_t)g.batch * H * W * C;
-
-  int dst0[4], dst1[4];
-  bool cval[4];
-#pragma unroll
-  for (int k = 0; k < 4; k++) {
-    const int cl = chan_of<CHMAP>(lane, k);
-    cval[k] = cl < cc;
-    const int ch = c0 + (cval[k] ? cl : 0);
-    if (VARIANT == JDET_ROI_RIROI) {
-      const int c = ch / nO, o = ch % nO;
-      const int ind_rot = (o - g.ind + nO) % nO;
-      const int ind_rot_plus = (ind_rot + 1 + nO) % nO;
-      dst0[k] = c * nO + ind_rot;
-      dst1[k] = c * nO + ind_rot_plus;
-    } else {
-      dst0[k] = ch;
-      dst1[k] = ch;
-    }
-  }
-
-  const int spb = g.grid_h * g.grid_w;
-  if (spb <= 0) return;  // count == 0: the reference divides by zero -> inf*0; nothing sane to add
-  const int nb = (nbins - wave + 3) >> 2;
-  const int bpc = spb <= 64 ? 64 / spb : 1;
-  const int passes = spb <= 64 ? 1 : (spb + 63) / 64;
-
-  auto lane_sample = [&](int kg, int pass) -> Sample {
-    int my_kb, my_r;
-    if (passes == 1) {
-      my_kb = lane / spb;
-      my_r = lane % spb;
-    } else {
-      my_kb = 0;
-      my_r = pass * 64 + lane;
-    }
-    const int my_bin = wave + 4 * (kg + my_kb);
-    const bool ok = my_kb < bpc && my_bin < nbins && my_r < spb;
-    const int iy = ok ? my_r / g.grid_w : 0;
-    const int ix = ok ? my_r % g.grid_w : 0;
-    const int bb = ok ? my_bin : 0;
-    Sample m = make_sample<VARIANT>(g, bb / PW, bb % PW, iy, ix, H, W);
-    // fold 1/count into the weights once per sample (reference: top*w/count per element)
-    m.w1 /= g.count;
-    m.w2 /= g.count;
-    m.w3 /= g.count;
-    m.w4 /= g.count;
-    return m;
-  };
-
-  for (int kg = 0; kg < nb; kg += bpc) {
-    Sample mine = lane_sample(kg, 0);
-    for (int kb = 0; kb < bpc && kg + kb < nb; kb++) {
-      const int bin = wave + 4 * (kg + kb);
-      float top[4];
-#pragma unroll
-      for (int k = 0; k < 4; k++) top[k] = cval[k] ? s_g[chan_of<CHMAP>(lane, k) * nbins + bin] : 0.f;
-      for (int pass = 0; pass < passes; pass++) {
-        if (passes > 1) mine = lane_sample(kg, pass);
-        const int lane0 = passes == 1 ? kb * spb : 0;
-        const int ns = passes == 1 ? spb : min(64, spb - pass * 64);
-        for (int j = 0; j < ns; j++) {
-          const Sample s = bcast(mine, lane0 + j);
-          if (!s.valid) continue;
-#pragma unroll
-          for (int k = 0; k < 4; k++) {
-            if (!cval[k]) continue;
-            const float g1 = top[k] * s.w1, g2 = top[k] * s.w2, g3 = top[k] * s.w3, g4 = top[k] * s.w4;
-            if (VARIANT == JDET_ROI_RIROI) {
-              unsafeAtomicAdd(img + (size_t)s.o1 * C + dst0[k], g1 * g.r_var);
-              unsafeAtomicAdd(img + (size_t)s.o2 * C + dst0[k], g2 * g.r_var);
-              unsafeAtomicAdd(img + (size_t)s.o3 * C + dst0[k], g3 * g.r_var);
-              unsafeAtomicAdd(img + (size_t)s.o4 * C + dst0[k], g4 * g.r_var);
-              unsafeAtomicAdd(img + (size_t)s.o1 * C + dst1[k], g1 * g.l_var);
-              unsafeAtomicAdd(img + (size_t)s.o2 * C + dst1[k], g2 * g.l_var);
-              unsafeAtomicAdd(img + (size_t)s.o3 * C + dst1[k], g3 * g.l_var);
-              unsafeAtomicAdd(img + (size_t)s.o4 * C + dst1[k], g4 * g.l_var);
-            } else {
-              unsafeAtomicAdd(img + (size_t)s.o1 * C + dst0[k], g1);
-              unsafeAtomicAdd(img + (size_t)s.o2 * C + dst0[k], g2);
-              unsafeAtomicAdd(img + (size_t)s.o3 * C + dst0[k], g3);
-              unsafeAtomicAdd(img + (size_t)s.o4 * C + dst0[k], g4);
-            }
-          }
-        }
-      }
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
-// XCD-aware spatial schedule.
-// The feature map (67 MB at 256x256x256 fp32) does not fit a 4 MiB XCD L2, and workgroup b runs
-// on XCD b % 8: with RoIs in arbitrary order every XCD streams the whole map through the fabric
-// (measured: FETCH 451 MB per launch for 67 MB of map, L2 hit 37 %).  This kernel buckets RoIs by
-// the Morton code of their centre cell (counting sort, one workgroup, O(R)), then deals
-// contiguous runs of the sorted list to the 8 XCDs: order[b] = sorted[start(b % 8) + b / 8].
-// Each XCD then sweeps one compact region of the map and concurrently resident workgroups are
-// spatial neighbours (measured: FETCH 139 MB, L2 hit 73 %).
-// ---------------------------------------------------------------------------------------------
-constexpr int kOrderThreads = 1024;
-constexpr int kOrderCellsLog2 = 5;                   // 32 x 32 cells per image
-constexpr int kOrderCells = 1 << (2 * kOrderCellsLog2);
-constexpr int kOrderMaxImages = 8;                   // bins in LDS: 8 * 1024 * 4 B = 32 KiB
-
-__device__ __forceinline__ unsigned morton2(unsigned x, unsigned y) {
-  auto spread = [](unsigned v) {
-    v &= 0xffff;
-    v = (v | (v << 8)) & 0x00ff00ff;
-    v = (v | (v << 4)) & 0x0f0f0f0f;
-    v = (v | (v << 2)) & 0x33333333;
-    v = (v | (v << 1)) & 0x55555555;
-    return v;
-  };
-  return spread(x) | (spread(y) << 1);
-}
-
-__global__ __launch_bounds__(kOrderThreads) void roi_order_kernel(const float* __restrict__ rois, int R,
-                                                                 int roi_cols, float spatial_scale, int N,
-                                                                 int H, int W, int32_t* __restrict__ order,
-                                                                 int32_t* __restrict__ sorted_tmp) {
-  constexpr int kKeep = 8;                      // RoIs per thread whose key stays in registers
-  constexpr int kLdsSorted = kKeep * kOrderThreads;  // R <= 8192: sorted list lives in LDS
-  __shared__ int s_bins[kOrderMaxImages * kOrderCells];
-  __shared__ int s_scan[kOrderThreads / 64];
-  __shared__ int s_sorted[kLdsSorted];
-  const int nimg = min(N, kOrderMaxImages);
-  const int nbins = nimg * kOrderCells;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int i = threadIdx.x; i < nbins; i += kOrderThreads) s_bins[i] = 0;
-  __syncthreads();
-  auto key_of = [&](int r) -> int {
-    const float* p = rois + (size_t)r * roi_cols;
-    float cx, cy;
-    if (roi_cols == 5) {
-      cx = 0.5f * (p[1] + p[3]) * spatial_scale;
-      cy = 0.5f * (p[2] + p[4]) * spatial_scale;
-    } else {
-      cx = p[1] * spatial_scale;
-      cy = p[2] * spatial_scale;
-    }
-    int b = (int)p[0];
-    b = min(max(b, 0), nimg - 1);
-    const float fx = fminf(fmaxf(cx / (float)W, 0.f), 0.999999f);
-    const float fy = fminf(fmaxf(cy / (float)H, 0.f), 0.999999f);
-    const unsigned ix = (unsigned)(fx * (1 << kOrderCellsLog2));
-    const unsigned iy = (unsigned)(fy * (1 << kOrderCellsLog2));
-    return b * kOrderCells + (int)morton2(ix, iy);
-  };
-  int mykey[kKeep];
-#pragma unroll
-  for (int i = 0; i < kKeep; i++) {
-    const int r = threadIdx.x + i * kOrderThreads;
-    mykey[i] = r < R ? key_of(r) : 0;
-    if (r < R) atomicAdd(&s_bins[mykey[i]], 1);
-  }
-  for (int r = threadIdx.x + kKeep * kOrderThreads; r < R; r += kOrderThreads) atomicAdd(&s_bins[key_of(r)], 1);
-  __syncthreads();
-  // exclusive scan of the bins: contiguous slice per thread, wave scan by DPP-style shuffles,
-  // one LDS hop across the 16 waves
-  const int per = (nbins + kOrderThreads - 1) / kOrderThreads;
-  const int lo = threadIdx.x * per, hi = min(lo + per, nbins);
-  int sum = 0;
-  for (int i = lo; i < hi; i++) sum += s_bins[i];
-  int incl = sum;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int v = __shfl_up(incl, off, 64);
-    if (lane >= off) incl += v;
-  }
-  if (lane == 63) s_scan[wave] = incl;
-  __syncthreads();
-  int wave_base = 0;
-  for (int w = 0; w < wave; w++) wave_base += s_scan[w];
-  int run = wave_base + incl - sum;
-  for (int i = lo; i < hi; i++) {
-    const int c = s_bins[i];
-    s_bins[i] = run;
-    run += c;
-  }
-  __syncthreads();
-  const bool in_lds = R <= kLdsSorted;
-#pragma unroll
-  for (int i = 0; i < kKeep; i++) {
-    const int r = threadIdx.x + i * kOrderThreads;
-    if (r < R) {
-      const int pos = atomicAdd(&s_bins[mykey[i]], 1);
-      if (in_lds) s_sorted[pos] = r; else sorted_tmp[pos] = r;
-    }
-  }
-  for (int r = threadIdx.x + kKeep * kOrderThreads; r < R; r += kOrderThreads)
-    sorted_tmp[atomicAdd(&s_bins[key_of(r)], 1)] = r;
-  if (!in_lds) __threadfence();  // global scratch is re-read by other waves: agent-scope release
-  __syncthreads();
-  // deal contiguous runs to the 8 XCDs (workgroup b -> XCD b % 8 is the observed dispatch rule;
-  // a different placement only costs speed): start(x) = sum_{y<x} ceil((R - y) / 8)
-  for (int b = threadIdx.x; b < R; b += kOrderThreads) {
-    const int x = b & 7, p = b >> 3;
-    int start = 0;
-#pragma unroll
-    for (int y = 0; y < 7; y++) start += y < x ? ((R - y + 7) >> 3) : 0;
-    order[b] = in_lds ? s_sorted[start + p]
-                      : __hip_atomic_load(sorted_tmp + start + p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-}
-
-// (Round 6, measured and removed: the same schedule from a multi-workgroup launch -- every workgroup computes all keys into
-// LDS and ranks its own 16 / 32 RoIs by counting, 8 / 16 lanes per RoI over (key << 13 | index) words, no inter-workgroup
-// exchange.  5.8 us with 63 workgroups, 7.2 us with 125 (rocprofv3) against 5.0 us for the counting sort above: the
-// R key computations every workgroup repeats cost what the serial chain costs.  profiles/r06_roi_plan_notes.md.)
-
-// ---------------------------------------------------------------------------------------------
-// NCHW <-> NHWC tiled transposes: per image a (C, HW) <-> (HW, C) matrix transpose.
-// ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void transpose_kernel(const float* __restrict__ x,
-                                                        float* __restrict__ y, int rows, int cols) {
-  // x: (batch, rows, cols) -> y: (batch, cols, rows); 32x32 tiles, +1 pad (conflict-free)
-  __shared__ float tile[32][33];
-  const size_t base = (size_t)blockIdx.z * rows * cols;
-  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;  // 32 x 8
-  const int c0 = blockIdx.x * 32, r0 = blockIdx.y * 32;
-#pragma unroll
-  for (int i = 0; i < 32; i += 8) {
-    const int rr = r0 + ty + i, ccol = c0 + tx;
-    if (rr < rows && ccol < cols) tile[ty + i][tx] = x[base + (size_t)rr * cols + ccol];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int i = 0; i < 32; i += 8) {
-    const int ccol = c0 + ty + i, rr = r0 + tx;
-    if (rr < rows && ccol < cols) y[base + (size_t)ccol * rows + rr] = tile[tx][ty + i];
-  }
-}
-
-int launch_transpose(const float* x, float* y, int batch, int rows, int cols, hipStream_t st) {
-  if (batch == 0 || rows == 0 || cols == 0) return JDET_OK;
-  dim3 grid(jdet_cdiv(cols, 32), jdet_cdiv(rows, 32), batch);
-  if (grid.y > 65535 || grid.z > 65535) return JDET_E_UNSUPPORTED;
-  hipLaunchKernelGGL(transpose_kernel, grid, dim3(256), 0, st, x, y, rows, cols);
+// The vector kernels: C % 4 == 0 and a map under 2 GiB per image.  NO = 0, or the orientation planes (4 / 8) of a
+// RiRoIAlign call, which are mixed in registers: once per bin on the merged path (rotated geometry), per sample in
+// the reference's order.
+template <int VARIANT, int NO>
+int launch_fwd_vec(const float* feat, const float* rois, float* out, int R, int C, int H, int W, int PH, int PW,
+                   float scale, int sample_num, const int32_t* order, hipStream_t st, bool out_cl, int mode) {
+  constexpr int V = NO ? JDET_ROI_ROTATED : VARIANT;
+  const dim3 grid(R, jdet_cdiv(C, kChunkC)), block(kFwdWaves * 64);
+  const size_t lds = (size_t)min(C, kChunkC) * PH * PW * sizeof(float);   // the (channel, bin) staging block of an NCHW result
+  const bool merged = sample_num == 2 && mode != kFwdReference && PH * PW <= 64 && (out_cl || lds >= kFwdListLds);
+  if (merged && out_cl)   // rolling-window tap loop, rows stored straight from registers
+    hipLaunchKernelGGL((roi_align_fwd_merged_kernel<V, kFwdWaves, 256, true, NO>), grid, block,
+                       NO ? kFwdListLds : kFwdClLds, st, feat, rois, out, C, H, W, PH, PW, scale, order);
+  else if (merged)
+    hipLaunchKernelGGL((roi_align_fwd_merged_kernel<V, kFwdWaves, 0, false, NO>), grid, block, lds, st, feat, rois, out,
+                       C, H, W, PH, PW, scale, order);
+  else if (out_cl)
+    hipLaunchKernelGGL((roi_align_fwd_vec_kernel<VARIANT, kFwdWaves, kFwdSG, true, NO>), grid, block, 16, st, feat,
+                       rois, out, C, H, W, PH, PW, scale, sample_num, order);
+  else
+    hipLaunchKernelGGL((roi_align_fwd_vec_kernel<VARIANT, kFwdWaves, kFwdSG, false, NO>), grid, block, lds, st, feat,
+                       rois, out, C, H, W, PH, PW, scale, sample_num, order);
   return jdet_launch_status();
-}
-
-// Tuning knobs of the vector forward path (A/B-able from the environment for profiling runs).
-int env_int(const char* name, int dflt) {
-  const char* v = getenv(name);
-  return v ? atoi(v) : dflt;
-}
-
-// Arithmetic of a forward call (an argument of the launchers, chosen by the ENTRY POINT -- there is no process-wide
-// mode): 0 = merged taps (the product entry points), 1 = reference operation order (the *_reference entry points:
-// bit-identical to the CPU oracle, the parity twin).  The measured alternatives live in libjdet_experimental.so, which
-// compiles this file with JDET_ROI_EXPERIMENTAL_MODES: 2 = merged taps through the channel-sliced kernels
-// (experimental/roi_align_sliced.h), 3 = taps deduplicated over a line of bins (experimental/roi_align_line.h).
-constexpr int kFwdMerged = 0, kFwdReference = 1, kFwdSliced = 2, kFwdLine = 3, kFwdStaged = 4, kFwdPair = 5;
-
-// footprint-staged forward (roi_align_stage.h): channels-last result, 2x2 samples per bin, PH, PW <= 8
-template <int VARIANT, int CPP, int P7>
-int launch_staged(const float* feat, const float* rois, float* out, int R, int C, int H, int W, int PH, int PW,
-                  float scale, const int32_t* order, hipStream_t st) {
-  using namespace jdet_roi_stage;
-  auto kern = roi_align_fwd_staged_kernel<VARIANT, CPP, P7>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       Layout<CPP>::kTotal);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
-  static const int abl = env_int("JDET_ROI_STAGE_ABL", 0);   // profiling: 1 prologue only, 2 no DMA, 4 no compute, 8 no stores
-  hipLaunchKernelGGL(kern, dim3(R), dim3(kThreads), Layout<CPP>::kTotal, st, feat, rois, out, C, H, W, PH, PW, scale,
-                     order, abl);
-  return jdet_launch_status();
-}
-
-inline bool staged_ok(int C, int PH, int PW, int sample_num, int cpp) {
-  return sample_num == 2 && PH <= 8 && PW <= 8 && C % cpp == 0;
-}
-
-// JDET_ROI_FWD_GRAN: which tap loop the channels-last merged forward runs (A/B and profiling; read once per process)
-inline int fwd_loop_switch() {
-  static const int v = env_int("JDET_ROI_FWD_GRAN", 256);
-  return v;
 }
 
 template <int VARIANT>
 int launch_fwd(const float* feat, const float* rois, float* out, int R, int C, int H, int W, int PH,
                int PW, float scale, int sample_num, int nO, const int32_t* order, hipStream_t st,
                bool out_cl = false, int mode = kFwdMerged) {
-  const int chunks = jdet_cdiv(C, kChunkC);
+  const bool vec_ok = (C % 4 == 0) && (size_t)H * W * C * 4 < (1ull << 31);
+  if constexpr (VARIANT == JDET_ROI_RIROI) {
+    if (vec_ok && nO == 8)
+      return launch_fwd_vec<VARIANT, 8>(feat, rois, out, R, C, H, W, PH, PW, scale, sample_num, order, st, out_cl, mode);
+    if (vec_ok && nO == 4)
+      return launch_fwd_vec<VARIANT, 4>(feat, rois, out, R, C, H, W, PH, PW, scale, sample_num, order, st, out_cl, mode);
+  } else {
+    if (vec_ok)
+      return launch_fwd_vec<VARIANT, 0>(feat, rois, out, R, C, H, W, PH, PW, scale, sample_num, order, st, out_cl, mode);
+  }
+  // channels-last output: vector kernels only (the callers check jdet_roi_align_forward_cl_supported)
+  if (out_cl) return JDET_E_UNSUPPORTED;
+  const dim3 grid(R, jdet_cdiv(C, kChunkC));
   const size_t lds = (size_t)min(C, kChunkC) * PH * PW * sizeof(float);
-  dim3 grid(R, chunks);
-  const bool vec = (C % 4 == 0) && VARIANT != JDET_ROI_RIROI && (size_t)H * W * C * 4 < (1ull << 31);
-  const int nbins = PH * PW;
-  const bool big_ok = (C % 4 == 0) && (size_t)H * W * C * 4 < (1ull << 31);
-  if (VARIANT == JDET_ROI_RIROI && big_ok && (nO == 4 || nO == 8)) {
-    // orientation planes mixed in registers.  Default: merged-tap kernel + one mix per bin; reference-order mode
-    // (or sampling other than 2x2): the per-sample kernel, bit-identical to the scalar one.
-    const bool merged = sample_num == 2 && mode != kFwdReference && nbins <= 64 && (out_cl || lds >= 8 * 2048);
-    const size_t lds_m = out_cl ? 8 * 2048 : lds, lds_v = out_cl ? 16 : lds;
-#ifdef JDET_ROI_EXPERIMENTAL_MODES
-#define JDET_PAIR_MODE_ON(mode_, PH_, PW_) ((mode_) == kFwdPair && pair_ok(PH_, PW_))
-#define JDET_PAIR_LAUNCH(NO_)                                                                                       \
-  hipLaunchKernelGGL((roi_align_fwd_pair_kernel<JDET_ROI_ROTATED, NO_>), grid, dim3(256), (size_t)36 * 1024, st, feat, \
-                     rois, out, C, H, W, PH, PW, scale, order)
-#else
-#define JDET_PAIR_MODE_ON(mode_, PH_, PW_) false
-#define JDET_PAIR_LAUNCH(NO_) (void)0
-#endif
-#define JDET_RI(NO_)                                                                                              \
-  do {                                                                                                            \
-    if (merged && out_cl && JDET_PAIR_MODE_ON(mode, PH, PW))                                                      \
-      JDET_PAIR_LAUNCH(NO_);                                                                                      \
-    else if (merged && out_cl && fwd_loop_switch() == 4)                                                          \
-      hipLaunchKernelGGL((roi_align_fwd_merged_kernel<JDET_ROI_ROTATED, 4, 0, true, NO_>), grid, dim3(256), lds_m, \
-                         st, feat, rois, out, C, H, W, PH, PW, scale, order, 0);                                  \
-    else if (merged && out_cl)                                                                                    \
-      hipLaunchKernelGGL((roi_align_fwd_merged_kernel<JDET_ROI_ROTATED, 4, 256, true, NO_>), grid, dim3(256), lds_m, \
-                         st, feat, rois, out, C, H, W, PH, PW, scale, order, 0);                                  \
-    else if (merged)                                                                                              \
-      hipLaunchKernelGGL((roi_align_fwd_merged_kernel<JDET_ROI_ROTATED, 4, 0, false, NO_>), grid, dim3(256), lds_m, \
-                         st, feat, rois, out, C, H, W, PH, PW, scale, order, 0);                                  \
-    else if (out_cl)                                                                                              \
-      hipLaunchKernelGGL((roi_align_fwd_vec_kernel<JDET_ROI_RIROI, 4, 4, 0, true, NO_>), grid, dim3(256), lds_v, st, \
-                         feat, rois, out, C, H, W, PH, PW, scale, sample_num, order);                             \
-    else                                                                                                          \
-      hipLaunchKernelGGL((roi_align_fwd_vec_kernel<JDET_ROI_RIROI, 4, 4, 0, false, NO_>), grid, dim3(256), lds_v, st, \
-                         feat, rois, out, C, H, W, PH, PW, scale, sample_num, order);                             \
-  } while (0)
-    if (nO == 8) JDET_RI(8);
-    else JDET_RI(4);
-#undef JDET_RI
-    return jdet_launch_status();
-  }
-  if (out_cl) {   // channels-last output: vector kernels only (the callers check jdet_roi_align_forward_cl_supported)
-    if (!vec) return JDET_E_UNSUPPORTED;
-    constexpr int V = VARIANT == JDET_ROI_RIROI ? JDET_ROI_ROTATED : VARIANT;
-    // (the merged kernel keeps its per-wave tap lists in the first 2 KiB / wave of the dynamic LDS block)
-    if (mode == kFwdStaged && staged_ok(C, PH, PW, sample_num, 64)) {
-      static const int cpp = env_int("JDET_ROI_STAGE_CPP", 64);
-      const bool p7 = PH == 7 && PW == 7;
-      if (cpp == 32)
-        return p7 ? launch_staged<V, 32, 1>(feat, rois, out, R, C, H, W, PH, PW, scale, order, st)
-                  : launch_staged<V, 32, 0>(feat, rois, out, R, C, H, W, PH, PW, scale, order, st);
-      return p7 ? launch_staged<V, 64, 1>(feat, rois, out, R, C, H, W, PH, PW, scale, order, st)
-                : launch_staged<V, 64, 0>(feat, rois, out, R, C, H, W, PH, PW, scale, order, st);
-    }
-    if (sample_num == 2 && mode != kFwdReference && nbins <= 64) {
-      // The LDS request caps the workgroups per CU at 4 (36 KiB each; the tap lists need 16): one workgroup fewer
-      // in flight per CU leaves the time where it is (59.4 vs 60.9 us at the north-star point) and cuts the reads
-      // beyond the L2 by 14 % (1.34 M vs 1.55 M 128-byte requests, profiles/r03_roi_pool_notes.md) -- fewer RoIs
-      // in flight, smaller working set.  JDET_ROI_FWD_LDS_KB overrides (profiling).
-      static const int lds_kb = env_int("JDET_ROI_FWD_LDS_KB", 36);
-      const size_t lds_cl = lds_kb > 16 ? (size_t)lds_kb * 1024 : 8 * 2048;
-#ifdef JDET_ROI_EXPERIMENTAL_MODES
-      if (mode == kFwdLine && PH <= kLineMaxBins && PW <= kLineMaxBins && nbins * 4 <= 256) {
-        // taps deduplicated over a line of bins (roi_align_line.h): 36 KiB of tables = 4 workgroups per CU as well
-        static const int line_batch16 = env_int("JDET_ROI_FWD_LINE_BATCH16", 0);     // (A/B runs: 16 rows per batch)
-        const size_t lds_ln = (size_t)kLineMaxBins * kLineSlots * (4 + 32);
-        if (PH <= 7 && PW <= 7 && !line_batch16)
-          hipLaunchKernelGGL((roi_align_fwd_line_kernel<V, 7, 8>), grid, dim3(256), lds_ln, st, feat, rois, out, C, H,
-                             W, PH, PW, scale, order);
-        else if (PH <= 7 && PW <= 7)
-          hipLaunchKernelGGL((roi_align_fwd_line_kernel<V, 7, 16>), grid, dim3(256), lds_ln, st, feat, rois, out, C, H,
-                             W, PH, PW, scale, order);
-        else
-          hipLaunchKernelGGL((roi_align_fwd_line_kernel<V, 8, 16>), grid, dim3(256), lds_ln, st, feat, rois, out, C, H,
-                             W, PH, PW, scale, order);
-      } else
-#endif
-      {
-        // product: the rolling-window tap loop (256).  4 / 2 / 1: the per-bin loop with that many rows per guarded group
-        // (4 = the product loop of rounds 1-5, bit-identical to the rolling window); +128: workgroup time stamps
-        const int gran = fwd_loop_switch();
-#ifdef JDET_ROI_EXPERIMENTAL_MODES
-        if (mode == kFwdPair && pair_ok(PH, PW)) {
-          hipLaunchKernelGGL((roi_align_fwd_pair_kernel<V, 0>), grid, dim3(256), lds_cl, st, feat, rois, out, C, H, W, PH,
-                             PW, scale, order);
-          return jdet_launch_status();
-        }
-#endif
-        if (gran == 2)
-          hipLaunchKernelGGL((roi_align_fwd_merged_kernel<V, 4, 32, true>), grid, dim3(256), lds_cl, st, feat, rois, out,
-                             C, H, W, PH, PW, scale, order, 0);
-        else if (gran == 1)
-          hipLaunchKernelGGL((roi_align_fwd_merged_kernel<V, 4, 64, true>), grid, dim3(256), lds_cl, st, feat, rois, out,
-                             C, H, W, PH, PW, scale, order, 0);
-        else if (gran == 128)                                        // (workgroup time stamps into the output rows)
-          hipLaunchKernelGGL((roi_align_fwd_merged_kernel<V, 4, 128, true>), grid, dim3(256), lds_cl, st, feat, rois, out,
-                             C, H, W, PH, PW, scale, order, 0);
-        else if (gran == 4)                                          // the per-bin loop of rounds 1-5
-          hipLaunchKernelGGL((roi_align_fwd_merged_kernel<V, 4, 0, true>), grid, dim3(256), lds_cl, st, feat, rois, out,
-                             C, H, W, PH, PW, scale, order, 0);
-        else if (gran == 768)                                        // prologue only (profiling)
-          hipLaunchKernelGGL((roi_align_fwd_merged_kernel<V, 4, 768, true>), grid, dim3(256), lds_cl, st, feat, rois, out,
-                             C, H, W, PH, PW, scale, order, 0);
-        else if (gran == 384)                                        // rolling window + stamps
-          hipLaunchKernelGGL((roi_align_fwd_merged_kernel<V, 4, 384, true>), grid, dim3(256), lds_cl, st, feat, rois, out,
-                             C, H, W, PH, PW, scale, order, 0);
-        else                                                         // rolling window (product)
-          hipLaunchKernelGGL((roi_align_fwd_merged_kernel<V, 4, 256, true>), grid, dim3(256), lds_cl, st, feat, rois, out,
-                             C, H, W, PH, PW, scale, order, 0);
-      }
-    }
-    else
-      hipLaunchKernelGGL((roi_align_fwd_vec_kernel<V, 4, 4, 0, true>), grid, dim3(256), 16, st, feat, rois, out, C, H,
-                         W, PH, PW, scale, sample_num, order);
-    return jdet_launch_status();
-  }
-  if (vec && sample_num == 2 && mode != kFwdReference && nbins <= 64 && lds >= 8 * 2048) {
-    constexpr int V = VARIANT == JDET_ROI_RIROI ? JDET_ROI_ROTATED : VARIANT;
-    static const int nw = env_int("JDET_ROI_FWD_WAVES", 4);
-    static const int abl = env_int("JDET_ROI_ABLATE", 0);  // profiling builds only
-    if (abl == 1)
-      hipLaunchKernelGGL((roi_align_fwd_merged_kernel<V, 4, 1>), grid, dim3(256), lds, st, feat, rois, out, C, H, W,
-                         PH, PW, scale, order, env_int("JDET_ROI_ABL_MASK", 63));
-    else if (abl == 4)
-      hipLaunchKernelGGL((roi_align_fwd_merged_kernel<V, 4, 4>), grid, dim3(256), lds, st, feat, rois, out, C, H, W,
-                         PH, PW, scale, order, env_int("JDET_ROI_ABL_MASK", 63));
-    else if (abl == 16)
-      hipLaunchKernelGGL((roi_align_fwd_merged_kernel<V, 4, 16>), grid, dim3(256), lds, st, feat, rois, out, C, H, W,
-                         PH, PW, scale, order, env_int("JDET_ROI_ABL_MASK", 63));
-    else if (abl == 8)
-      hipLaunchKernelGGL((roi_align_fwd_merged_kernel<V, 4, 8>), grid, dim3(256), lds, st, feat, rois, out, C, H, W,
-                         PH, PW, scale, order, env_int("JDET_ROI_ABL_MASK", 63));
-    else if (abl == 5)
-      hipLaunchKernelGGL((roi_align_fwd_merged_kernel<V, 4, 5>), grid, dim3(256), lds, st, feat, rois, out, C, H, W,
-                         PH, PW, scale, order, env_int("JDET_ROI_ABL_MASK", 63));
-    else if (nw == 8)
-      hipLaunchKernelGGL((roi_align_fwd_merged_kernel<V, 8>), grid, dim3(512), lds, st, feat, rois, out, C, H, W,
-                         PH, PW, scale, order, env_int("JDET_ROI_ABL_MASK", 63));
-    else if (nw == 2 && nbins <= 32)
-      hipLaunchKernelGGL((roi_align_fwd_merged_kernel<V, 2>), grid, dim3(128), lds, st, feat, rois, out, C, H, W,
-                         PH, PW, scale, order, env_int("JDET_ROI_ABL_MASK", 63));
-    else
-      hipLaunchKernelGGL((roi_align_fwd_merged_kernel<V, 4>), grid, dim3(256), lds, st, feat, rois, out, C, H, W,
-                         PH, PW, scale, order, env_int("JDET_ROI_ABL_MASK", 63));
-  } else if (vec) {
-    constexpr int V = VARIANT == JDET_ROI_RIROI ? JDET_ROI_ROTATED : VARIANT;  // never RiRoI here
-    static const int nw = env_int("JDET_ROI_FWD_WAVES", 4);
-    static const int sg = env_int("JDET_ROI_FWD_SG", 4);
-    static const int abl = env_int("JDET_ROI_ABLATE", 0);  // profiling builds only
-#define JDET_FWD(NW, SG, ABL)                                                                       \
-  hipLaunchKernelGGL((roi_align_fwd_vec_kernel<V, NW, SG, ABL>), grid, dim3(NW * 64), lds, st, feat, \
-                     rois, out, C, H, W, PH, PW, scale, sample_num, order)
-    if (abl == 1 && nw == 8) JDET_FWD(8, 4, 1);
-    else if (abl == 2 && nw == 8) JDET_FWD(8, 4, 2);
-    else if (abl == 3 && nw == 8) JDET_FWD(8, 4, 3);
-    else if (abl == 4 && nw == 8) JDET_FWD(8, 4, 4);
-    else if (abl == 7 && nw == 8) JDET_FWD(8, 4, 7);
-    else if (abl == 1) JDET_FWD(4, 4, 1);
-    else if (abl == 2) JDET_FWD(4, 4, 2);
-    else if (abl == 3) JDET_FWD(4, 4, 3);
-    else if (abl == 4) JDET_FWD(4, 4, 4);
-    else if (abl == 7) JDET_FWD(4, 4, 7);
-    else if (nw == 8 && sg == 8) JDET_FWD(8, 8, 0);
-    else if (nw == 8) JDET_FWD(8, 4, 0);
-    else if (nw == 16) JDET_FWD(16, 4, 0);
-    else if (sg == 8) JDET_FWD(4, 8, 0);
-    else if (sg == 2) JDET_FWD(4, 2, 0);
-    else JDET_FWD(4, 4, 0);
-#undef JDET_FWD
-  } else if (C % 4 == 0 && VARIANT != JDET_ROI_RIROI) {
+  if (C % 4 == 0 && VARIANT != JDET_ROI_RIROI)
     hipLaunchKernelGGL((roi_align_fwd_kernel<VARIANT, 0>), grid, dim3(kBlock), lds, st, feat, rois, out,
                        C, H, W, PH, PW, scale, sample_num, nO, order);
-  } else {
+  else
     hipLaunchKernelGGL((roi_align_fwd_kernel<VARIANT, 1>), grid, dim3(kBlock), lds, st, feat, rois, out,
                        C, H, W, PH, PW, scale, sample_num, nO, order);
-  }
   return jdet_launch_status();
-}
-
-template <int VARIANT>
-int launch_bwd(const float* gout, const float* rois, float* gin, int R, int C, int H, int W, int PH,
-               int PW, float scale, int sample_num, int nO, const int32_t* order, hipStream_t st) {
-  const int chunks = jdet_cdiv(C, kChunkC);
-  const size_t lds = (size_t)min(C, kChunkC) * PH * PW * sizeof(float);
-  hipLaunchKernelGGL((roi_align_bwd_kernel<VARIANT>), dim3(R, chunks), dim3(kBlock), lds, st, gout,
-                     rois, gin, C, H, W, PH, PW, scale, sample_num, nO, order);
-  return jdet_launch_status();
-}
-
-
-#ifdef JDET_ROI_EXPERIMENTAL_MODES
-// ---- channel-sliced forward (experimental/roi_align_sliced.h): measured slower than the RoI-stationary kernels
-// (profiles/r04_roi_fwd_notes.md), reachable through libjdet_experimental.so only ----
-bool sliced_ok(int variant, int R, int N, int C, int H, int W, int PH, int PW, int sample_num, int nO) {
-  if (sample_num != 2) return false;
-  const long nbins = (long)PH * PW;
-  if (nbins < jdet_roi_sliced::kItemsPerWave || C % jdet_roi_sliced::kSliceC != 0) return false;
-  if ((size_t)N * H * W * C * 4 >= (1ull << 31) || (long)R * nbins >= (1L << 30)) return false;
-  if (variant == JDET_ROI_RIROI && nO != 4 && nO != 8) return false;
-  return true;
-}
-
-template <int VARIANT, int NO>
-int launch_sliced(const float* feat, const float* rois, float* out, int R, int N, int C, int H, int W, int PH, int PW,
-                  float scale, int nO, void* ws, hipStream_t st) {
-  using namespace jdet_roi_sliced;
-  const int nbins = PH * PW;
-  const PlanWs w = plan_carve(ws, R, nbins);
-  // EXPERIMENT (profiling): JDET_ROI_SLICED_PLANAR=1 reads `feat` as [slice][pixel][32 channels] (every slice one
-  // contiguous plane) instead of NHWC -- the caller must pass a map permuted that way
-  static const int planar = env_int("JDET_ROI_SLICED_PLANAR", 0);
-  const int pix_bytes = planar ? kSliceC * 4 : C * 4;
-  const unsigned slice_stride = planar ? (unsigned)((size_t)N * H * W * kSliceC * 4) : (unsigned)(kSliceC * 4);
-  hipLaunchKernelGGL((roi_sort_plan_kernel<VARIANT>), dim3(1 + (R + 3) / 4), dim3(1024), 0, st, rois, R, scale, N,
-                     pix_bytes, H, W, PH, PW, nO, w.hdr, w.order, w.rrec, w.ent);
-  const int nslices = C / kSliceC;
-  const long items = (long)R * nbins;
-#define JDET_SL(B_, P_, NW_)                                                                                          \
-  hipLaunchKernelGGL((roi_pool_sliced_kernel<NO, B_, P_, NW_>),                                                       \
-                     dim3((unsigned)(nslices * ((items + NW_ * kItemsPerWave - 1) / (NW_ * kItemsPerWave)))),         \
-                     dim3(NW_ * 64), 0, st, feat, w.order, w.rrec, w.ent, out, R, N, C, H * W, nbins, nslices, slice_stride)
-  if constexpr (NO == 0) {   // tuning knobs (profiling runs)
-    static const int batch = env_int("JDET_ROI_SLICED_BATCH", 8), pred = env_int("JDET_ROI_SLICED_PRED", 0),
-                     nw = env_int("JDET_ROI_SLICED_WAVES", 4);
-    if (nw == 16 && batch == 4 && pred == 1) JDET_SL(4, 1, 16);
-    else if (nw == 16) JDET_SL(8, 0, 16);
-    else if (nw == 8 && batch == 4 && pred == 1) JDET_SL(4, 1, 8);
-    else if (nw == 1 && batch == 4 && pred == 1) JDET_SL(4, 1, 1);
-    else if (batch == 4 && pred == 0) JDET_SL(4, 0, 4);
-    else if (batch == 16 && pred == 0) JDET_SL(16, 0, 4);
-    else if (batch == 4 && pred == 1) JDET_SL(4, 1, 4);
-    else if (batch == 8 && pred == 1) JDET_SL(8, 1, 4);
-    else JDET_SL(8, 0, 4);
-  } else {
-    JDET_SL(8, 0, 4);
-  }
-#undef JDET_SL
-  return jdet_launch_status();
-}
-
-#endif  // JDET_ROI_EXPERIMENTAL_MODES
-
-int check_common(int variant, const void* a, const void* b, const void* c, int N, int C, int H,
-                 int W, int R, int PH, int PW, int n_orient) {
-  if (variant < 0 || variant > 4) return JDET_E_BADARG;
-  if (N < 0 || C <= 0 || H <= 0 || W <= 0 || R < 0 || PH <= 0 || PW <= 0) return JDET_E_BADARG;
-  if (R > 0 && (!a || !b || !c)) return JDET_E_BADARG;
-  if (PH * PW > 256) return JDET_E_UNSUPPORTED;
-  if (variant == JDET_ROI_RIROI && (n_orient <= 0 || C % n_orient != 0)) return JDET_E_BADARG;
-  if ((long)H * W >= (1L << 30)) return JDET_E_UNSUPPORTED;
-  return JDET_OK;
 }
 
 }  // namespace

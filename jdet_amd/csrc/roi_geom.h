@@ -1,8 +1,10 @@
-// Geometry shared by the RoIAlign forward / backward kernels (roi_align.hip, roi_align_bwd.hip):
+// Geometry shared by the RoIAlign forward / backward kernels (roi_align_fwd.h, roi_align_bwd.hip):
 // per-RoI scalar prologue and per-sample bilinear setup of the five dialects, with the reference's
-// literal fp32/fp64 mix.  Reference lines: roi_align_rotated.py:L21-59, L70-118 (v1: _v1.py:L89-134;
+// literal fp32/fp64 mix; the argument checks and the dialect dispatch of their entry points.  Reference lines: roi_align_rotated.py:L21-59, L70-118 (v1: _v1.py:L89-134;
 // RiRoI: riroi_align.py:L105-113; horizontal: roi_align.py:L105-132).
 #pragma once
+#include <type_traits>
+
 #include "common.h"
 
 namespace jdet_roi {
@@ -214,5 +216,29 @@ __device__ __forceinline__ int chan_of(int lane, int k) {
   return CHMAP == 0 ? lane * 4 + k : lane + 64 * k;
 }
 
+// Argument checks shared by the forward and backward entry points.
+inline int check_common(int variant, const void* a, const void* b, const void* c, int N, int C, int H,
+                        int W, int R, int PH, int PW, int n_orient) {
+  if (variant < 0 || variant > 4) return JDET_E_BADARG;
+  if (N < 0 || C <= 0 || H <= 0 || W <= 0 || R < 0 || PH <= 0 || PW <= 0) return JDET_E_BADARG;
+  if (R > 0 && (!a || !b || !c)) return JDET_E_BADARG;
+  if (PH * PW > 256) return JDET_E_UNSUPPORTED;
+  if (variant == JDET_ROI_RIROI && (n_orient <= 0 || C % n_orient != 0)) return JDET_E_BADARG;
+  if ((long)H * W >= (1L << 30)) return JDET_E_UNSUPPORTED;
+  return JDET_OK;
+}
+
+// Run-time dialect -> template argument: calls f(std::integral_constant<int, VARIANT>{}) for a variant that
+// check_common has accepted.
+template <typename F>
+inline int with_variant(int variant, F&& f) {
+  switch (variant) {
+    case JDET_ROI_ROTATED: return f(std::integral_constant<int, JDET_ROI_ROTATED>{});
+    case JDET_ROI_ROTATED_V1: return f(std::integral_constant<int, JDET_ROI_ROTATED_V1>{});
+    case JDET_ROI_RIROI: return f(std::integral_constant<int, JDET_ROI_RIROI>{});
+    case JDET_ROI_HBB_V0: return f(std::integral_constant<int, JDET_ROI_HBB_V0>{});
+    default: return f(std::integral_constant<int, JDET_ROI_HBB_V1>{});
+  }
+}
 
 }  // namespace jdet_roi

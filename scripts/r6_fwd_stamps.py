@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """Round 6: where the time of the product RoIAlign forward goes ACROSS the chip -- workgroup start / end stamps.
 
-JDET_ROI_FWD_GRAN=128 launches roi_align_fwd_merged_kernel<..., ABL = 128>: every workgroup writes wall_clock64() at its
-start and end, HW_ID, XCC_ID and blockIdx into the first words of its RoI's first output row (a profiling build: that
-row is garbage afterwards).  This script runs the north-star launch a few times and prints, from the last one:
+With JDET_ROI_FWD_GRAN=128, forward mode 0 of jdet_roi_align_forward_cl_mode (libjdet_experimental.so: the product
+arithmetic with the profiling builds available) launches roi_align_fwd_merged_kernel<..., ABL = 128>: every workgroup
+writes wall_clock64() at its start and end, HW_ID, XCC_ID and blockIdx into the first words of its RoI's first output
+row (a profiling build: that row is garbage afterwards).  This script runs the north-star launch a few times and prints, from the last one:
 kernel span, per-XCD first start / last end, the busy fraction of the (XCD, CU) workgroup slots over the span, the
 distribution of workgroup durations, and how much of the span is the ragged end (time after the LAST workgroup start).
 
@@ -17,25 +18,27 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 os.environ.setdefault("JDET_ROI_FWD_GRAN", "128")
+from jdet_amd import _experimental as X  # noqa: E402
 from jdet_amd import _lib as L  # noqa: E402
+from jdet_amd.ops._roi_common import spatial_order  # noqa: E402
 from tests import inputs as I  # noqa: E402
 
 
 def main():
     R = int(sys.argv[1]) if len(sys.argv) > 1 else 2000
     dev = torch.device("cuda:0")
-    lib = L.lib()
+    xlib = X.lib()
     rng = np.random.default_rng(1000)
     g = torch.Generator(device="cpu").manual_seed(0)
     feat = torch.randn((1, 256, 256, 256), generator=g).to(dev).contiguous(memory_format=torch.channels_last)
     rois_np = I.rois_from_obbs(I.random_obbs(rng, R), np.zeros(R))
     rois = torch.from_numpy(rois_np).to(dev)
     out = torch.empty((R, 256, 7, 7), device=dev).contiguous(memory_format=torch.channels_last)
-    wsb = lib.jdet_roi_align_forward_cl_workspace(R, 7, 7)
-    ws = torch.empty((wsb,), dtype=torch.uint8, device=dev)
-    for _ in range(20):
-        L.check(lib.jdet_roi_align_forward_cl(0, feat.data_ptr(), 1, 256, 256, 256, rois.data_ptr(), R, 7, 7, 0.25, 2, 1,
-                                              out.data_ptr(), ws.data_ptr(), wsb, L.stream_ptr(feat)), "fwd_cl")
+    for _ in range(20):   # (the schedule the product entry point computes for itself: R >= 64)
+        order = spatial_order(rois, 0.25, 1, 256, 256) if R >= 64 else None
+        L.check(xlib.jdet_roi_align_forward_cl_mode(0, 0, feat.data_ptr(), 1, 256, 256, 256, rois.data_ptr(), R, 7, 7, 0.25, 2,
+                                                    1, order.data_ptr() if order is not None else None, out.data_ptr(), None,
+                                                    0, L.stream_ptr(feat)), "fwd_cl_mode 0")
     torch.cuda.synchronize()
     # memory of `out` is (R, 7, 7, 256): the stamps are the first 8 words of row (r, bin 0)
     words = out.permute(0, 2, 3, 1).reshape(R, -1)[:, :8].contiguous().view(torch.int32).cpu().numpy().astype(np.int64)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Round 6: the footprint-staged RoIAlign forward (csrc/roi_align_stage.h, LDS-DMA) next to the product kernel.
+"""Round 6: the footprint-staged RoIAlign forward (csrc/experimental/roi_align_stage.h, LDS-DMA) next to the product kernel.
     python scripts/r6_stage.py parity            small dialect x shape cases against the CPU oracle + the product kernel
     python scripts/r6_stage.py time [reps]       north-star point: order kernel + forward, HIP events
 Environment: JDET_ROI_STAGE_CPP=64|32 (channels per pass)."""

@@ -301,7 +301,7 @@ def test_single_level_dialects_at_full_size_against_the_reference_kernels(dev, d
     the RoI's size: up to 10 x 10 taps per bin; no plan exists for it: the self-contained channels-last backward).
     Default against reference-order arithmetic under adaptive sampling: measured 0.0 at grids up to 10 x 10 for both
     dialects -- the tap merge exists for sample_num == 2 only, the default entry runs the reference's chain otherwise
-    (csrc/roi_align_impl.inc) -- so the 2e-6 of the fixed grids is kept as the bound."""
+    (csrc/roi_align_fwd.h) -- so the 2e-6 of the fixed grids is kept as the bound."""
     case = RCS.single_case(dialect, R, sampling, seed)
     trig = dialect in RCS.TRIG
     rois = torch.from_numpy(case["rois"]).to(dev)

@@ -1,4 +1,4 @@
-"""GPU parity of the footprint-staged RoIAlign forward (round 6: csrc/roi_align_stage.h -- distinct pixels of a line of
+"""GPU parity of the footprint-staged RoIAlign forward (round 6: csrc/experimental/roi_align_stage.h -- distinct pixels of a line of
 bins fetched once by LDS-DMA, taps served from LDS; libjdet_experimental.so, forward mode 4): against the CPU oracle and
 the product's merged-tap kernel, merged-tap tolerance (2e-6 abs on N(0,1) maps: same weights, another summation order).
 Covers the five dialects without orientation planes, several images, masked RoIs (rows untouched), RoIs over the border,
