@@ -593,6 +593,30 @@ int jdet_oriented_delta_decode(const float* rois, const float* deltas, long n, i
 int jdet_oriented_delta_encode(const float* rois, const float* gt, long n, const float* means5, const float* stds5,
                                float* out, jdet_stream_t stream);
 
+/* Box codecs of the Gliding Vertex detector, one fused launch each (csrc/box_codec_gliding.hip).  Replace the Jittor
+ * tensor programs models/boxes/coder.py:L148-205 (GVFixCoder), L213-228 (GVRatioCoder), L242-320
+ * (GVDeltaXYWHBBoxCoder) and the target / decode passes of models/roi_heads/gliding_head.py:L287-325, L355-379.
+ *   jdet_gliding_targets: rois (n,4) horizontal, gt polygons (n,8) -> bbox_targets (n,4) = delta encode of the roi
+ *     against poly2hbb(poly), fix_targets (n,4) = (dt, dr, dd, dl), all 1 on the rows the reference's h_mask marks,
+ *     ratio_targets (n,1) = |shoelace area| / area of the enclosing box.  Ties between extreme vertices resolve to the
+ *     lowest vertex index (this project's rule: Jittor's argmax tie order is not in the reference tree).
+ *   jdet_gliding_decode: per (row, class): delta decode of bbox_pred (n, 4*ncls) with the clamp to (max_h, max_w)
+ *     [<= 0: no clamp], GVFixCoder.decode with fix_pred (n, 4*ncls), the box itself (hbb2poly) where ratio_pred
+ *     (n, ncls) > ratio_thr, every (x, y) divided by scale4 = (sx, sy, sx, sy) -> polys (n, 8*ncls).
+ *   jdet_gv_delta_encode / _decode: the horizontal delta codec alone (the RPN encodes against horizontal gts);
+ *     decode is class-wise: deltas (n, 4*ncls) -> (n, 4*ncls).
+ * means4 / stds4 / scale4 are HOST pointers to 4 floats.  n == 0: no-op. */
+int jdet_gliding_targets(const float* rois_hbb, const float* gt_polys, long n, const float* means4, const float* stds4,
+                         float* bbox_targets, float* fix_targets, float* ratio_targets, jdet_stream_t stream);
+int jdet_gliding_decode(const float* rois_hbb, const float* bbox_pred, const float* fix_pred, const float* ratio_pred,
+                        long n, int ncls, const float* means4, const float* stds4, float wh_ratio_clip, float max_h,
+                        float max_w, float ratio_thr, const float* scale4, float* out_polys, jdet_stream_t stream);
+int jdet_gv_delta_encode(const float* rois_hbb, const float* gt_hbb, long n, const float* means4, const float* stds4,
+                         float* out4, jdet_stream_t stream);
+int jdet_gv_delta_decode(const float* rois_hbb, const float* deltas, long n, int ncls, const float* means4,
+                         const float* stds4, float wh_ratio_clip, float max_h, float max_w, float* out,
+                         jdet_stream_t stream);
+
 /* Dense anchor targets: replaces the index-list scatter of anchor_target_single
  * (models/boxes/anchor_target.py:L137-168) for the PseudoSampler case.  gt_inds (A) is the assigner's
  * output (0 negative, -1 ignored, i+1 = gt i); every anchor gets label (gt_labels[i] or 1 when gt_labels is

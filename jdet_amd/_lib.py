@@ -137,6 +137,10 @@ SIGNATURES = {
     "jdet_midpoint_offset_encode": (_i, [_p, _p, _l, _p, _p, _p, _p]),
     "jdet_oriented_delta_decode": (_i, [_p, _p, _l, _i, _p, _p, _f, _p, _p]),
     "jdet_oriented_delta_encode": (_i, [_p, _p, _l, _p, _p, _p, _p]),
+    "jdet_gliding_targets": (_i, [_p, _p, _l, _p, _p, _p, _p, _p, _p]),
+    "jdet_gliding_decode": (_i, [_p, _p, _p, _p, _l, _i, _p, _p, _f, _f, _f, _f, _p, _p, _p]),
+    "jdet_gv_delta_encode": (_i, [_p, _p, _l, _p, _p, _p, _p]),
+    "jdet_gv_delta_decode": (_i, [_p, _p, _l, _i, _p, _p, _f, _f, _f, _p, _p]),
     "jdet_anchor_targets_rotated": (_i, [_p, _p, _p, _p, _i, _i, _p, _p, _f, _p, _p, _p, _p, _p, _p]),
     "jdet_anchor_targets_rotated_boxes": (_i, [_p, _p, _p, _i, _i, _f, _p, _p, _p, _p, _p, _p]),
     "jdet_obb2hbb2obb": (_i, [_p, _i, _i, _p, _p]),

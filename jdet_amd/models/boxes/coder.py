@@ -1,8 +1,12 @@
 """BBox coders of the named configs.  Mirrors python/jdet/models/boxes/coder.py:
 `DeltaXYWHABBoxCoder` L76-141."""
+import math
+
 import torch
 
 from jdet_amd import _lib as L
+from jdet_amd.ops.bbox_transforms import hbb2poly, poly2hbb
+from jdet_amd.utils.general import const_like
 from jdet_amd.utils.registry import BOXES
 
 from .box_ops import bbox2delta_rotated, delta2bbox_rotated
@@ -190,3 +194,221 @@ class OrientedDeltaXYWHTCoder:
         gtheta = regular_theta(dtheta + ptheta)
         new_bboxes = regular_obb(torch.stack([gx, gy, gw, gh, gtheta], dim=-1))
         return new_bboxes.view_as(pred_bboxes)
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# Gliding Vertex coders (coder.py:L143-320 of the reference).  The fused launches live in csrc/box_codec_gliding.hip;
+# the torch compositions below are what runs on the host, in float64 and wherever a gradient is asked for.  The Jittor
+# programs themselves cannot be run here (Jittor is not importable): the compositions are pinned by the restatement in
+# tests/gliding_ref.py and its closed forms only.
+
+def _fused32_ok(*ts):
+    """`_fused_ok` for float32 inputs only: the kernels are fp32, and a float64 caller is promised the float64
+    composition, not a silent down-cast"""
+    return _fused_ok(*ts) and all(t.dtype == torch.float32 for t in ts)
+
+
+def _max_hw(max_shape):
+    """(h, w) of a `max_shape` argument as floats; (0, 0) = no clamp"""
+    if max_shape is None:
+        return 0.0, 0.0
+    return float(max_shape[0]), float(max_shape[1])
+
+
+def gv_delta_encode(bboxes, gt_bboxes, means, stds):
+    """GVDeltaXYWHBBoxCoder.encode as a torch composition (coder.py:L248-268)"""
+    px = (bboxes[..., 0] + bboxes[..., 2]) * 0.5
+    py = (bboxes[..., 1] + bboxes[..., 3]) * 0.5
+    pw = bboxes[..., 2] - bboxes[..., 0]
+    ph = bboxes[..., 3] - bboxes[..., 1]
+    gx = (gt_bboxes[..., 0] + gt_bboxes[..., 2]) * 0.5
+    gy = (gt_bboxes[..., 1] + gt_bboxes[..., 3]) * 0.5
+    gw = gt_bboxes[..., 2] - gt_bboxes[..., 0]
+    gh = gt_bboxes[..., 3] - gt_bboxes[..., 1]
+    deltas = torch.stack([(gx - px) / pw, (gy - py) / ph, torch.log(gw / pw), torch.log(gh / ph)], dim=-1)
+    return (deltas - deltas.new_tensor(means).unsqueeze(0)) / deltas.new_tensor(stds).unsqueeze(0)
+
+
+def gv_delta_decode(bboxes, pred_bboxes, means, stds, max_shape=None, wh_ratio_clip=16 / 1000):
+    """GVDeltaXYWHBBoxCoder.decode as a torch composition (coder.py:L280-318)"""
+    reps = pred_bboxes.size(1) // 4
+    d = pred_bboxes * pred_bboxes.new_tensor(stds).repeat(1, reps) + pred_bboxes.new_tensor(means).repeat(1, reps)
+    dx, dy, dw, dh = d[:, 0::4], d[:, 1::4], d[:, 2::4], d[:, 3::4]
+    max_ratio = abs(math.log(wh_ratio_clip))
+    dw = dw.clamp(min=-max_ratio, max=max_ratio)
+    dh = dh.clamp(min=-max_ratio, max=max_ratio)
+    px = ((bboxes[:, 0] + bboxes[:, 2]) * 0.5).unsqueeze(1)
+    py = ((bboxes[:, 1] + bboxes[:, 3]) * 0.5).unsqueeze(1)
+    pw = (bboxes[:, 2] - bboxes[:, 0]).unsqueeze(1)
+    ph = (bboxes[:, 3] - bboxes[:, 1]).unsqueeze(1)
+    gw, gh = pw * dw.exp(), ph * dh.exp()
+    gx, gy = px + pw * dx, py + ph * dy
+    x1, y1, x2, y2 = gx - gw * 0.5, gy - gh * 0.5, gx + gw * 0.5, gy + gh * 0.5
+    max_h, max_w = _max_hw(max_shape)
+    if max_h > 0 and max_w > 0:
+        x1, x2 = x1.clamp(min=0, max=max_w), x2.clamp(min=0, max=max_w)
+        y1, y2 = y1.clamp(min=0, max=max_h), y2.clamp(min=0, max=max_h)
+    return torch.stack([x1, y1, x2, y2], dim=-1).view_as(pred_bboxes)
+
+
+def gv_fix_encode(polys):
+    """GVFixCoder.encode as a torch composition (coder.py:L152-185).  torch.argmax / argmin return the FIRST extreme:
+    the lowest-vertex-index tie rule of the fused kernel."""
+    xs, ys = polys[:, 0::2], polys[:, 1::2]
+    max_x, max_x_idx = xs.max(dim=1).values, xs.argmax(dim=1)
+    min_x, min_x_idx = xs.min(dim=1).values, xs.argmin(dim=1)
+    max_y, max_y_idx = ys.max(dim=1).values, ys.argmax(dim=1)
+    min_y, min_y_idx = ys.min(dim=1).values, ys.argmin(dim=1)
+    pick = lambda v, idx: v.gather(1, idx[:, None])[:, 0]   # noqa: E731
+    t_x, t_y = pick(xs, min_y_idx), pick(ys, min_y_idx)
+    r_x, r_y = pick(xs, max_x_idx), pick(ys, max_x_idx)
+    d_x = pick(xs, max_y_idx)
+    l_y = pick(ys, min_x_idx)
+    dt = (t_x - min_x) / (max_x - min_x)
+    dr = (r_y - min_y) / (max_y - min_y)
+    dd = (max_x - d_x) / (max_x - min_x)
+    dl = (max_y - l_y) / (max_y - min_y)
+    h_mask = (t_y - r_y == 0) | (r_x - d_x == 0)
+    fix = torch.stack([dt, dr, dd, dl], dim=1)
+    return torch.where(h_mask[:, None], torch.ones_like(fix), fix)
+
+
+def gv_fix_decode(hbboxes, fix_deltas):
+    """GVFixCoder.decode as a torch composition (coder.py:L188-205): (n, 4C), (n, 4C) -> (n, 8C)"""
+    x1, y1, x2, y2 = hbboxes[:, 0::4], hbboxes[:, 1::4], hbboxes[:, 2::4], hbboxes[:, 3::4]
+    w, h = x2 - x1, y2 - y1
+    pred_t_x = x1 + w * fix_deltas[:, 0::4]
+    pred_r_y = y1 + h * fix_deltas[:, 1::4]
+    pred_d_x = x2 - w * fix_deltas[:, 2::4]
+    pred_l_y = y2 - h * fix_deltas[:, 3::4]
+    return torch.stack([pred_t_x, y1, x2, pred_r_y, pred_d_x, y2, x1, pred_l_y], dim=-1).flatten(1)
+
+
+def gv_ratio_encode(polys):
+    """GVRatioCoder.encode as a torch composition (coder.py:L215-228)"""
+    xs, ys = polys[:, 0::2], polys[:, 1::2]
+    h_areas = (xs.max(dim=1).values - xs.min(dim=1).values) * (ys.max(dim=1).values - ys.min(dim=1).values)
+    areas = torch.zeros_like(h_areas)
+    for i in range(4):
+        j = (i + 1) % 4
+        areas = areas + 0.5 * (xs[:, i] * ys[:, j] - xs[:, j] * ys[:, i])
+    return (torch.abs(areas) / h_areas)[:, None]
+
+
+def gliding_targets(rois, polys, means, stds, fused=None):
+    """the target pass of GlidingHead for matched (roi, gt polygon) rows (gliding_head.py:L309-321): bbox_targets (n,4),
+    fix_targets (n,4), ratio_targets (n,1) -- one launch (jdet_gliding_targets) on a device, the three compositions
+    elsewhere.  `fused`: None = decide by `_fused32_ok`, False = the composition."""
+    if (fused is None and _fused32_ok(rois, polys) and rois.shape[1] == 4 and polys.shape[1] == 8) or fused:
+        r, p = L.f32c(rois), L.f32c(polys)
+        n = r.shape[0]
+        assert tuple(r.shape) == (n, 4) and tuple(p.shape) == (n, 8)
+        bbox_t = torch.empty((n, 4), dtype=torch.float32, device=r.device)
+        fix_t = torch.empty((n, 4), dtype=torch.float32, device=r.device)
+        ratio_t = torch.empty((n, 1), dtype=torch.float32, device=r.device)
+        L.check(L.lib().jdet_gliding_targets(L.ptr(r), L.ptr(p), n, L.vecn(means, 4), L.vecn(stds, 4), L.ptr(bbox_t),
+                                             L.ptr(fix_t), L.ptr(ratio_t), L.stream_ptr(r)), "jdet_gliding_targets")
+        return bbox_t, fix_t, ratio_t
+    return gv_delta_encode(rois, poly2hbb(polys), means, stds), gv_fix_encode(polys), gv_ratio_encode(polys)
+
+
+def gliding_decode(rois, bbox_pred, fix_pred, ratio_pred, means, stds, max_shape=None, wh_ratio_clip=16 / 1000,
+                   ratio_thr=0.8, scale=(1., 1., 1., 1.), fused=None):
+    """the decode pass of GlidingHead (gliding_head.py:L362-374): rois (n,4), bbox_pred / fix_pred (n,4C), ratio_pred
+    (n,C) -> polygons (n, 8C), divided by scale.repeat(2).  One launch (jdet_gliding_decode) on a device."""
+    if (fused is None and _fused32_ok(rois, bbox_pred, fix_pred, ratio_pred) and rois.shape[1] == 4) or fused:
+        r, b, f, q = L.f32c(rois), L.f32c(bbox_pred), L.f32c(fix_pred), L.f32c(ratio_pred)
+        n, ncls = q.shape
+        assert b.shape == (n, 4 * ncls) and f.shape == (n, 4 * ncls) and tuple(r.shape) == (n, 4)
+        out = torch.empty((n, 8 * ncls), dtype=torch.float32, device=r.device)
+        max_h, max_w = _max_hw(max_shape)
+        L.check(L.lib().jdet_gliding_decode(L.ptr(r), L.ptr(b), L.ptr(f), L.ptr(q), n, ncls, L.vecn(means, 4),
+                                            L.vecn(stds, 4), float(wh_ratio_clip), max_h, max_w, float(ratio_thr),
+                                            L.vecn(scale, 4), L.ptr(out), L.stream_ptr(r)), "jdet_gliding_decode")
+        return out
+    boxes = gv_delta_decode(rois, bbox_pred, means, stds, max_shape, wh_ratio_clip)
+    polys = gv_fix_decode(boxes, fix_pred)
+    boxes = boxes.view(*ratio_pred.shape, 4)
+    polys = polys.view(*ratio_pred.shape, 8)
+    polys = torch.where((ratio_pred > ratio_thr)[..., None], hbb2poly(boxes), polys)
+    polys = polys / polys.new_tensor(scale).repeat(2)
+    return polys.view(polys.size(0), -1)
+
+
+@BOXES.register_module()
+class GVFixCoder:
+    """Gliding offsets (coder.py:L143-205): the positions of the top / right / bottom / left vertex of a quadrilateral
+    along the sides of its enclosing box, as fractions (dt, dr, dd, dl); rows the reference's `h_mask` marks (the top
+    and right vertex share a y, or the right and bottom vertex an x: a horizontal rectangle) are all 1."""
+
+    def __init__(self):
+        pass
+
+    def encode(self, polys):
+        assert polys.size(1) == 8
+        if _fused32_ok(polys):
+            # the fused launch computes the three target groups together; a dummy unit roi keeps its delta encode
+            # finite.
+            # Not the hot path: the head takes all three from ONE `gliding_targets` call; a standalone coder call pays a
+            # launch of its own and drops the two outputs it does not return
+            rois = const_like((0., 0., 1., 1.), polys).expand(polys.shape[0], 4)
+            return gliding_targets(rois, polys, (0.,) * 4, (1.,) * 4, fused=True)[1]
+        return gv_fix_encode(polys)
+
+    def decode(self, hbboxes, fix_deltas):
+        return gv_fix_decode(hbboxes, fix_deltas)
+
+
+@BOXES.register_module()
+class GVRatioCoder:
+    """Obliquity ratio (coder.py:L208-231): |polygon area| / area of its enclosing box."""
+
+    def __init__(self):
+        pass
+
+    def encode(self, polys):
+        assert polys.size(1) == 8
+        if _fused32_ok(polys):       # a launch of its own, as in GVFixCoder.encode: the head uses `gliding_targets`
+            rois = const_like((0., 0., 1., 1.), polys).expand(polys.shape[0], 4)
+            return gliding_targets(rois, polys, (0.,) * 4, (1.,) * 4, fused=True)[2]
+        return gv_ratio_encode(polys)
+
+    def decode(self, bboxes, bboxes_pred):
+        raise NotImplementedError
+
+
+@BOXES.register_module()
+class GVDeltaXYWHBBoxCoder:
+    """Horizontal (dx, dy, dw, dh) codec of the Gliding Vertex RPN and head (coder.py:L233-320); decode is class-wise
+    and clamps to `max_shape` = (h, w)."""
+
+    def __init__(self, target_means=(0., 0., 0., 0.), target_stds=(1., 1., 1., 1.)):
+        self.means = target_means
+        self.stds = target_stds
+
+    def encode(self, bboxes, gt_bboxes):
+        assert bboxes.size(0) == gt_bboxes.size(0)
+        assert bboxes.size(-1) == gt_bboxes.size(-1) == 4
+        assert bboxes.size() == gt_bboxes.size()
+        if _fused32_ok(bboxes, gt_bboxes):
+            a, g = L.f32c(bboxes), L.f32c(gt_bboxes)
+            out = torch.empty_like(a)
+            L.check(L.lib().jdet_gv_delta_encode(L.ptr(a), L.ptr(g), a.shape[0], L.vecn(self.means, 4),
+                                                 L.vecn(self.stds, 4), L.ptr(out), L.stream_ptr(a)),
+                    "jdet_gv_delta_encode")
+            return out
+        return gv_delta_encode(bboxes.float() if bboxes.dtype != torch.float64 else bboxes,
+                               gt_bboxes.float() if gt_bboxes.dtype != torch.float64 else gt_bboxes,
+                               self.means, self.stds)
+
+    def decode(self, bboxes, pred_bboxes, max_shape=None, wh_ratio_clip=16 / 1000):
+        assert pred_bboxes.size(0) == bboxes.size(0)
+        if _fused32_ok(bboxes, pred_bboxes) and bboxes.shape[1] == 4 and pred_bboxes.shape[1] % 4 == 0:
+            a, d = L.f32c(bboxes), L.f32c(pred_bboxes)
+            out = torch.empty_like(d)
+            max_h, max_w = _max_hw(max_shape)
+            L.check(L.lib().jdet_gv_delta_decode(L.ptr(a), L.ptr(d), d.shape[0], d.shape[1] // 4,
+                                                 L.vecn(self.means, 4), L.vecn(self.stds, 4), float(wh_ratio_clip),
+                                                 max_h, max_w, L.ptr(out), L.stream_ptr(d)), "jdet_gv_delta_decode")
+            return out
+        return gv_delta_decode(bboxes, pred_bboxes, self.means, self.stds, max_shape, wh_ratio_clip)

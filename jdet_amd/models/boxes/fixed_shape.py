@@ -113,14 +113,23 @@ def dense_anchor_targets(anchors, inside, gts_for_assign, gts_for_encode, assign
 
 
 def proposal_table(boxes, scores, level_ids, level_sizes, alive, nms_thresh, nms_post_per_level, rows,
-                   nms_across_levels=False, invalid_score=-1.0, payload=None):
+                   nms_across_levels=False, invalid_score=-1.0, payload=None, global_nms=False):
     """Candidates of all levels (each level's slice sorted by descending score) -> a table of exactly `rows` rows
     [box..., score] sorted by score; rows beyond the survivors carry `invalid_score`.  Per-level NMS is ONE launch
     (the level id as label); `nms_post_per_level` caps the survivors of each level (None: no cap); with
     `nms_across_levels` a second, label-free pass runs over the survivors.  `boxes`: horizontal (x1,y1,x2,y2), what
-    the NMS sees; `payload` (default: the boxes): what the table rows carry."""
+    the NMS sees; `payload` (default: the boxes): what the table rows carry.
+    `global_nms`: ONE label-free pass over all candidates in descending score instead of the per-level pass
+    (`jt.nms` on the concatenated dets, gliding_rpn_head.py:L173-176); `nms_post_per_level` / `nms_across_levels` do
+    not apply then."""
     from jdet_amd.ops.nms import nms_keep_mask
     low = torch.full_like(scores, -2.0)
+    if global_nms:
+        assert nms_post_per_level is None and not nms_across_levels
+        far = boxes.new_full((4,), -1.0e4)
+        keep, _ = nms_keep_mask(torch.where(alive[:, None], boxes, far[None, :]), scores, nms_thresh,
+                                visit_order=torch.argsort(scores, descending=True, stable=True))
+        return _table_rows(boxes, scores, keep & alive, rows, invalid_score, payload)
     # The candidates arrive level by level, descending score inside a level: that IS the visiting order (no device
     # sort).  Dropped boxes (too small) are shrunk to a point far outside the image: they overlap nothing, so they
     # suppress nothing that is kept (the reference removes them before the NMS), and are removed below.
@@ -138,6 +147,11 @@ def proposal_table(boxes, scores, level_ids, level_sizes, alive, nms_thresh, nms
     if nms_across_levels:
         keep2, _ = nms_keep_mask(boxes, torch.where(ok, scores, low), nms_thresh)
         ok = ok & keep2
+    return _table_rows(boxes, scores, ok, rows, invalid_score, payload)
+
+
+def _table_rows(boxes, scores, ok, rows, invalid_score, payload):
+    """the best `rows` surviving candidates as table rows [box..., score], padded with `invalid_score` rows"""
     ranked = torch.where(ok, scores, torch.full_like(scores, invalid_score))
     k = min(rows, ranked.shape[0])
     top_scores, top = torch.topk(ranked, k)

@@ -6,3 +6,5 @@ from .kfiou_rotated_retina_head import KFIoURRetinaHead  # noqa: F401
 from .rbbox_head import BBoxHeadRbbox  # noqa: F401
 from .convfc_rbbox_head import ConvFCBBoxHeadRbbox, SharedFCBBoxHeadRbbox  # noqa: F401
 from .fasterrcnn_head import AnchorHead, FasterrcnnHead  # noqa: F401
+from .gliding_rpn_head import GlidingRPNHead  # noqa: F401
+from .gliding_head import GlidingHead  # noqa: F401

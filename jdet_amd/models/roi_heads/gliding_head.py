@@ -1,0 +1,233 @@
+"""Gliding Vertex RoI head.
+
+Contract of python/jdet/models/roi_heads/gliding_head.py:L10-456 (constructor arguments and defaults, parameter names
+`fc1 / fc2 / cls_score / bbox_pred / fix_pred / ratio_pred`, loss keys `gliding_cls_loss / gliding_bbox_loss /
+gliding_fix_loss / gliding_ratio_loss`, inference output `(polys (k,8), scores (k,), labels (k,))` per image, labels
+0-based): assign the horizontal proposals (+ the gts themselves) to `target["hboxes"]` by IoU, sample 512 RoIs per
+image (25 % positives), pool them with horizontal ROIAlign on four FPN levels, two FC layers, a (C+1)-way classifier
+(background = last class) and three class-specific regressors: 4 box deltas (GVDeltaXYWHBBoxCoder against the
+enclosing box of the matched polygon), 4 gliding offsets (GVFixCoder, through a sigmoid) and the obliquity ratio
+(GVRatioCoder, through a sigmoid).  Inference decodes the box, glides the four vertices along its sides, falls back to
+the box itself where the predicted ratio exceeds `ratio_thr`, and runs a polygon NMS per class.
+
+Execution (this file's own; the reference builds per-image SamplingResult index lists, L405-427, and runs the three
+encodes per image as 60-80 elementwise launches, L287-325):
+  * the RPN hands over a proposal TABLE per image -- always `nms_post` rows [x1, y1, x2, y2, score], padding rows with
+    score < 0 -- and everything downstream keeps fixed shapes (models/boxes/fixed_shape.py: `sample_stage_rows`):
+    unused rows point at a small dummy box and carry weight 0.  No nonzero / boolean indexing / `.any()` / `.item()`
+    in the train step, so no device -> host round trip.
+  * the targets of ALL images' rows come from one launch (`jdet_gliding_targets`, csrc/box_codec_gliding.hip), the
+    inference decode of an image from one launch (`jdet_gliding_decode`).
+  * the losses are weighted sums over the fixed row set: positives carry weight 1, everything else 0; with no
+    positive row a regression loss is 0 with a zero gradient (the reference's `pred.sum() * 0`, L246-283).
+  * RoI features arrive channels-last; `fc1` consumes them in that order (`RoIFeatureLinear`), checkpoints keep the
+    reference's weight order.
+  * `get_bboxes(..., rescale=False)`: the reference's `execute` never asks for the rescale (L448), so the division by
+    the scale factor (L369-373) runs only when a caller passes `rescale=True`.
+"""
+import torch
+import torch.nn.functional as F
+from torch import nn
+
+from jdet_amd.models.boxes.coder import gliding_decode, gliding_targets
+from jdet_amd.models.boxes.fixed_shape import sample_stage_rows
+from jdet_amd.ops.bbox_transforms import obb2poly
+from jdet_amd.ops.linear import Linear
+from jdet_amd.ops.nms_poly import multiclass_poly_nms
+from jdet_amd.utils.general import const_like
+from jdet_amd.utils.registry import BOXES, HEADS, LOSSES, ROI_EXTRACTORS, build_from_cfg
+
+from .roi_feature_linear import RoIFeatureLinear
+
+
+@HEADS.register_module()
+class GlidingHead(nn.Module):
+    def __init__(self, num_classes=15, in_channels=256, representation_dim=1024, pooler_resolution=7,
+                 pooler_scales=[1 / 4., 1 / 8., 1 / 16., 1 / 32., 1 / 64.], pooler_sampling_ratio=0, score_thresh=0.05,
+                 nms_thresh=0.1, detections_per_img=2000, box_weights=(10., 10., 5., 5.),
+                 assigner=dict(type="MaxIoUAssigner", pos_iou_thr=0.5, neg_iou_thr=0.5, min_pos_iou=0.5,
+                               ignore_iof_thr=-1, match_low_quality=False,
+                               iou_calculator=dict(type="BboxOverlaps2D")),
+                 sampler=dict(type="RandomSampler", num=512, pos_fraction=0.25, neg_pos_ub=-1,
+                              add_gt_as_proposals=True),
+                 bbox_coder=dict(type="GVDeltaXYWHBBoxCoder", target_means=(.0, .0, .0, .0),
+                                 target_stds=(0.1, 0.1, 0.2, 0.2)),
+                 fix_coder=dict(type="GVFixCoder"), ratio_coder=dict(type="GVRatioCoder"),
+                 bbox_roi_extractor=dict(type="SingleRoIExtractor",
+                                         roi_layer=dict(type="ROIAlign", output_size=7, sampling_ratio=2, version=1),
+                                         out_channels=256, featmap_strides=[4, 8, 16, 32]),
+                 cls_loss=dict(type="CrossEntropyLoss"),
+                 bbox_loss=dict(type="SmoothL1Loss", beta=1.0, loss_weight=1.0),
+                 fix_loss=dict(type="SmoothL1Loss", beta=1.0 / 3.0, loss_weight=1.0),
+                 ratio_loss=dict(type="SmoothL1Loss", beta=1.0 / 3.0, loss_weight=16.0),
+                 with_bbox=True, with_shared_head=False, start_bbox_type="hbb", end_bbox_type="poly",
+                 with_avg_pool=False, pos_weight=-1, reg_class_agnostic=False, ratio_thr=0.8, max_per_img=2000):
+        super().__init__()
+        assert with_bbox and not with_shared_head and not with_avg_pool
+        assert start_bbox_type == "hbb" and end_bbox_type == "poly", \
+            "the Gliding Vertex configuration (horizontal proposals -> polygon detections)"
+        self.representation_dim, self.in_channels, self.num_classes = representation_dim, in_channels, num_classes
+        self.pooler_resolution, self.pooler_scales = pooler_resolution, pooler_scales
+        self.pooler_sampling_ratio, self.box_weights = pooler_sampling_ratio, box_weights
+        self.score_thresh, self.nms_thresh, self.detections_per_img = score_thresh, nms_thresh, detections_per_img
+        self.start_bbox_type, self.end_bbox_type = start_bbox_type, end_bbox_type
+        self.pos_weight, self.reg_class_agnostic = pos_weight, reg_class_agnostic
+        self.ratio_thr, self.max_per_img = ratio_thr, max_per_img
+        self.assigner = build_from_cfg(assigner, BOXES)
+        assert self.assigner.ignore_iof_thr <= 0, "ignore regions are not part of the Gliding Vertex configuration"
+        self.sampler = build_from_cfg(sampler, BOXES)          # carries num / pos_fraction / neg_pos_ub / add_gt
+        self.bbox_coder = build_from_cfg(bbox_coder, BOXES)
+        self.fix_coder = build_from_cfg(fix_coder, BOXES)
+        self.ratio_coder = build_from_cfg(ratio_coder, BOXES)
+        self.bbox_roi_extractor = build_from_cfg(bbox_roi_extractor, ROI_EXTRACTORS)
+        self.cls_loss = build_from_cfg(cls_loss, LOSSES)
+        self.bbox_loss = build_from_cfg(bbox_loss, LOSSES)
+        self.fix_loss = build_from_cfg(fix_loss, LOSSES)
+        self.ratio_loss = build_from_cfg(ratio_loss, LOSSES)
+        self._init_layers()
+        self.init_weights()
+
+    # ------------------------------------------------------------------ layers
+    def _init_layers(self):
+        n_out = 1 if self.reg_class_agnostic else self.num_classes
+        self.fc1 = RoIFeatureLinear(self.in_channels, self.pooler_resolution * self.pooler_resolution,
+                                    self.representation_dim)
+        self.fc2 = Linear(self.representation_dim, self.representation_dim)
+        self.cls_score = Linear(self.representation_dim, self.num_classes + 1)
+        self.bbox_pred = Linear(self.representation_dim, n_out * 4)
+        self.fix_pred = Linear(self.representation_dim, n_out * 4)
+        self.ratio_pred = Linear(self.representation_dim, n_out * 1)
+
+    def init_weights(self):
+        for m in (self.fc1, self.fc2):
+            nn.init.xavier_uniform_(m.weight)
+            nn.init.constant_(m.bias, 0)
+        nn.init.normal_(self.cls_score.weight, 0, 0.01)
+        nn.init.constant_(self.cls_score.bias, 0)
+        for m in (self.bbox_pred, self.fix_pred, self.ratio_pred):
+            nn.init.normal_(m.weight, 0, 0.001)
+            nn.init.constant_(m.bias, 0)
+
+    def forward_single(self, feats, rois):
+        """rois (R, 5) [image index, x1, y1, x2, y2] -> scores (R, C+1), bbox deltas (R, 4C), fixes (R, 4C), ratios
+        (R, C)  (L185-211)"""
+        x = self.bbox_roi_extractor(feats[:self.bbox_roi_extractor.num_inputs], rois)
+        x = F.relu(self.fc1(x))
+        x = F.relu(self.fc2(x))
+        return self.cls_score(x), self.bbox_pred(x), self.fix_pred(x).sigmoid(), self.ratio_pred(x).sigmoid()
+
+    # ------------------------------------------------------------------ training
+    @staticmethod
+    def _dummy_box(like):
+        return const_like([4.0, 4.0, 12.0, 12.0], like)
+
+    @staticmethod
+    def gt_polys(target):
+        """the gt polygons of one image: `target["polys"]`, or the corners of `target["rboxes"]` where the key is
+        absent"""
+        polys = target.get("polys")
+        return obb2poly(target["rboxes"]) if polys is None else polys
+
+    def sample(self, table, target):
+        """proposal table (P, 5) of one image -> its `num` sampled rows (StageRows) and their matched gt polygons
+        (num, 8) [the polygon of gt 0 off the positives]"""
+        gt_labels = (target["labels"] - 1).long()         # 0-based, background = num_classes (L394)
+        rows = sample_stage_rows(table[:, :4], table[:, 4] >= 0, target["hboxes"], gt_labels, self.assigner,
+                                 self.sampler, self._dummy_box(table), background_label=self.num_classes)
+        return rows, self.gt_polys(target)[rows.matched]
+
+    def targets(self, per_image, fused=None):
+        """[(StageRows, matched polygons)] -> labels (R,) long, label_weights (R,), bbox_targets (R,4), fix_targets
+        (R,4), ratio_targets (R,1), pos (R,) bool, valid (R,) bool over the R = images * num rows (L287-353); the three
+        encodes of every image's rows are ONE launch"""
+        boxes = torch.cat([r.boxes for r, _ in per_image])
+        polys = torch.cat([p for _, p in per_image])
+        pos = torch.cat([r.is_pos for r, _ in per_image])
+        valid = torch.cat([r.valid for r, _ in per_image])
+        labels = torch.cat([r.labels for r, _ in per_image])
+        pw = 1.0 if self.pos_weight <= 0 else self.pos_weight
+        label_weights = valid.float() * torch.where(pos, torch.full_like(valid, pw, dtype=torch.float32),
+                                                    torch.ones_like(valid, dtype=torch.float32))
+        bbox_t, fix_t, ratio_t = gliding_targets(boxes, polys, self.bbox_coder.means, self.bbox_coder.stds, fused=fused)
+        zero = lambda t: torch.where(pos[:, None], t, torch.zeros_like(t))   # noqa: E731
+        return labels, label_weights, zero(bbox_t), zero(fix_t), zero(ratio_t), pos, valid
+
+    def _class_rows(self, pred, labels, width):
+        """class-specific predictions (R, C*width) -> the (R, width) of each row's label (L231-238)"""
+        if self.reg_class_agnostic:
+            return pred.view(pred.size(0), width)
+        cls_of_row = labels.clamp(max=self.num_classes - 1)
+        pred = pred.view(pred.size(0), -1, width)
+        return pred.gather(1, cls_of_row[:, None, None].expand(-1, 1, width))[:, 0]
+
+    def loss(self, cls_score, bbox_pred, fix_pred, ratio_pred, labels, label_weights, bbox_targets, fix_targets,
+             ratio_targets, pos, valid):
+        losses = dict()
+        losses["gliding_cls_loss"] = self.cls_loss(
+            cls_score, labels, label_weights, avg_factor=torch.clamp((label_weights > 0).sum().float(), min=1.0))
+        # positives only, normalised by the number of sampled rows (`bbox_targets.size(0)`, L240-281)
+        n_rows = torch.clamp(valid.sum().float(), min=1.0)
+        w = pos.float()[:, None]
+        losses["gliding_bbox_loss"] = self.bbox_loss(self._class_rows(bbox_pred, labels, 4), bbox_targets,
+                                                     w.repeat(1, 4), avg_factor=n_rows)
+        losses["gliding_fix_loss"] = self.fix_loss(self._class_rows(fix_pred, labels, 4), fix_targets,
+                                                   w.repeat(1, 4), avg_factor=n_rows)
+        losses["gliding_ratio_loss"] = self.ratio_loss(self._class_rows(ratio_pred, labels, 1), ratio_targets,
+                                                       w.clone(), avg_factor=n_rows)
+        return losses
+
+    def forward_train(self, feats, proposal_tables, targets):
+        per_image = [self.sample(t, tg) for t, tg in zip(proposal_tables, targets)]
+        rois = torch.cat([torch.cat([r.boxes.new_full((r.boxes.shape[0], 1), float(i)), r.boxes], dim=1)
+                          for i, (r, _) in enumerate(per_image)])
+        with torch.no_grad():
+            tgt = self.targets(per_image)
+        return self.loss(*self.forward_single(feats, rois), *tgt)
+
+    # ------------------------------------------------------------------ inference
+    def get_results(self, polys, scores):
+        """polys (R, 8C) decoded, scores (R, C+1) -> (dets (k,9) [poly8, score], labels (k,))  (L153-183)"""
+        polys = polys.view(scores.size(0), -1, 8)
+        if polys.shape[1] == 1:
+            polys = polys.expand(-1, scores.size(1) - 1, 8)
+        fg = scores[:, :-1]
+        hit = fg > self.score_thresh
+        labels = hit.nonzero()[:, 1]                  # inference output has a data-dependent length
+        if labels.numel() == 0:
+            return polys.new_zeros((0, 9)), polys.new_zeros((0,), dtype=torch.long)
+        if self.nms_thresh is None:
+            return torch.cat([polys[hit], fg[hit].unsqueeze(1)], dim=1), labels
+        return multiclass_poly_nms(polys[hit], fg[hit], labels, self.nms_thresh)
+
+    def get_bboxes(self, rois, cls_score, bbox_pred, fix_pred, ratio_pred, img_shape, scale_factor, rescale=False,
+                   alive=None):
+        """L355-379; rois (R, 4).  `alive` (R,) bool: padding rows of a proposal table score 0 everywhere"""
+        scores = F.softmax(cls_score, dim=1)
+        if alive is not None:
+            scores = scores * alive[:, None].float()
+        scale = (1.0,) * 4
+        if rescale:
+            scale = (float(scale_factor),) * 4 if isinstance(scale_factor, (int, float)) else \
+                tuple(float(s) for s in scale_factor)
+        polys = gliding_decode(rois, bbox_pred.detach(), fix_pred.detach(), ratio_pred.detach(), self.bbox_coder.means,
+                               self.bbox_coder.stds, max_shape=img_shape, ratio_thr=self.ratio_thr, scale=scale)
+        return self.get_results(polys, scores.detach())
+
+    def forward_test(self, feats, proposal_tables, targets):
+        results = []
+        for i, (table, target) in enumerate(zip(proposal_tables, targets)):
+            alive = table[:, 4] >= 0
+            boxes = torch.where(alive[:, None], table[:, :4], self._dummy_box(table)[None, :])
+            rois = torch.cat([boxes.new_full((boxes.shape[0], 1), float(i)), boxes], dim=1)
+            cls_score, bbox_pred, fixes, ratios = self.forward_single(feats, rois)
+            dets, labels = self.get_bboxes(boxes, cls_score, bbox_pred, fixes, ratios, target["img_size"],
+                                           target["scale_factor"], alive=alive)
+            results.append((dets[:, :8], dets[:, 8], labels))
+        return results
+
+    def forward(self, x, proposal_list, targets):
+        if self.training:
+            return self.forward_train(x, proposal_list, targets)
+        return self.forward_test(x, proposal_list, targets)
+
+    execute = forward

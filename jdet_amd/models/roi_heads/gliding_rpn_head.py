@@ -1,0 +1,136 @@
+"""Gliding Vertex RPN head (horizontal anchors, horizontal proposals, two-way softmax objectness).
+
+Contract of python/jdet/models/roi_heads/gliding_rpn_head.py:L16-389 (constructor arguments and defaults, parameter
+names `rpn_conv / rpn_cls / rpn_reg`, loss keys `loss_rpn_cls` / `loss_rpn_bbox` as per-level lists,
+`forward(features, targets) -> (proposals per image, losses)`): 3x3 conv + 1x1 classifier (A * 2 channels, channel =
+a * 2 + class) + 1x1 regression (A * 4); targets = MaxIoUAssigner on the anchors inside the image vs
+`target["hboxes"]`, RandomSampler(256), GVDeltaXYWHBBoxCoder, label 1 on the sampled positives and 0 elsewhere;
+proposals = per-level top `nms_pre` by softmax(...)[:, 1], decode with `max_shape`, `min_bbox_size` filter, then ONE
+label-free NMS over the concatenation in descending score (`jt.nms` on the concatenated dets, L173-176 -- not per
+level), best `nms_post`.
+
+The execution is the fixed-shape, sync-free one of `OrientedRPNHead` (the reference builds per-image index lists with
+nonzero / boolean masks / randperm, L227-274, L100-178): targets are dense over ALL anchors of an image
+(models/boxes/fixed_shape.py), the sample counts that normalise the losses stay on the device, and every image yields
+a proposal TABLE of exactly `nms_post` rows [x1, y1, x2, y2, score] sorted by score, padding rows with score -1.
+"""
+import torch
+from torch import nn
+
+from jdet_amd.ops.conv_igemm import conv_module
+from jdet_amd.models.boxes.anchor_target import anchor_inside_flags
+from jdet_amd.models.boxes.fixed_shape import dense_anchor_targets, proposal_table
+from jdet_amd.models.utils.level_pack import run_levels
+from jdet_amd.ops import conv_igemm
+from jdet_amd.utils.registry import BOXES, HEADS, LOSSES, build_from_cfg
+
+INVALID_SCORE = -1.0   # score of a padding row in a proposal table
+
+
+@HEADS.register_module()
+class GlidingRPNHead(nn.Module):
+    def __init__(self, in_channels, num_classes=2, min_bbox_size=0, nms_thresh=0.7, nms_pre=2000, nms_post=2000,
+                 feat_channels=256,
+                 anchor_generator=dict(type="AnchorGenerator", scales=[4, 8, 16, 32], ratios=[0.5, 1.0, 2.0],
+                                       strides=[8, 16, 32, 64, 128]),
+                 bbox_coder=dict(type="GVDeltaXYWHBBoxCoder", target_means=(.0, .0, .0, .0),
+                                 target_stds=(1.0, 1.0, 1.0, 1.0)),
+                 loss_cls=dict(type="CrossEntropyLoss", loss_weight=1.0),
+                 loss_bbox=dict(type="L1Loss", loss_weight=1.0),
+                 assigner=dict(type="MaxIoUAssigner", pos_iou_thr=0.7, neg_iou_thr=0.3, min_pos_iou=0.3,
+                               ignore_iof_thr=-1),
+                 sampler=dict(type="RandomSampler", num=256, pos_fraction=0.5, neg_pos_ub=-1,
+                              add_gt_as_proposals=False)):
+        super().__init__()
+        assert num_classes == 2, "objectness = a two-way softmax per anchor (L136-141)"
+        self.in_channels, self.feat_channels, self.num_classes = in_channels, feat_channels, num_classes
+        self.min_bbox_size, self.nms_thresh, self.nms_pre, self.nms_post = min_bbox_size, nms_thresh, nms_pre, nms_post
+        self.bbox_coder = build_from_cfg(bbox_coder, BOXES)
+        self.loss_cls = build_from_cfg(loss_cls, LOSSES)
+        self.loss_bbox = build_from_cfg(loss_bbox, LOSSES)
+        self.assigner = build_from_cfg(assigner, BOXES)
+        self.sampler = build_from_cfg(sampler, BOXES)     # carries num / pos_fraction / neg_pos_ub
+        assert self.assigner.ignore_iof_thr <= 0, "ignore regions are not part of the Gliding Vertex configuration"
+        self.anchor_generator = build_from_cfg(anchor_generator, BOXES)
+        self.num_anchors = self.anchor_generator.num_base_anchors[0]
+        self.rpn_conv = nn.Conv2d(in_channels, feat_channels, 3, padding=1)
+        self.rpn_cls = nn.Conv2d(feat_channels, self.num_anchors * num_classes, 1)
+        self.rpn_reg = nn.Conv2d(feat_channels, self.num_anchors * 4, 1)
+
+    # ------------------------------------------------------------------ network
+    def forward_single(self, x, mask=None):
+        """`mask` is part of `run_levels`' callback signature (the gap mask of a packed input); the 1x1 layers below
+        read no neighbours, so a packed input needs none here"""
+        x = conv_igemm.conv3x3_module(self.rpn_conv, x, relu=True)
+        return conv_module(self.rpn_cls, x), conv_module(self.rpn_reg, x)
+
+    @staticmethod
+    def _per_anchor(t, width):
+        """(N, A*width, H, W) -> (N, H*W*A, width): the anchor order of grid_anchors (location-major, A fastest)"""
+        return t.permute(0, 2, 3, 1).reshape(t.shape[0], -1, width)
+
+    # ------------------------------------------------------------------ targets (dense over all anchors)
+    def loss(self, cls_scores, bbox_preds, targets):
+        sizes = [tuple(c.shape[-2:]) for c in cls_scores]
+        assert len(sizes) == self.anchor_generator.num_levels
+        dev = cls_scores[0].device
+        level_anchors = self.anchor_generator.grid_anchors(sizes, device=dev)
+        anchors = torch.cat(level_anchors)
+        per_image = []
+        for target in targets:
+            valid = torch.cat(self.anchor_generator.valid_flags(sizes, target["pad_shape"], device=dev))
+            inside = anchor_inside_flags(anchors, valid, target["img_size"][:2], allowed_border=0)
+            gt = target["hboxes"]
+            # label 1 on the sampled positives, 0 elsewhere (L250-261); pos_weight is fixed at 1 there
+            per_image.append(dense_anchor_targets(anchors, inside, gt, gt, self.assigner, self.sampler,
+                                                  self.bbox_coder.encode, 4, 0, -1))
+        labels, label_w, box_t, box_w = (torch.stack([p[k] for p in per_image]) for k in range(4))
+        # sum over images of max(#pos, 1) + max(#neg, 1)  (L292-293, L364), kept on the device
+        n_samples = sum(torch.clamp(p[4], min=1) + torch.clamp(p[5], min=1) for p in per_image).float()
+        losses_cls, losses_bbox, start = [], [], 0
+        for cls, reg, lvl in zip(cls_scores, bbox_preds, level_anchors):
+            sl = slice(start, start + lvl.shape[0])
+            start += lvl.shape[0]
+            score = self._per_anchor(cls, self.num_classes).reshape(-1, self.num_classes)
+            losses_cls.append(self.loss_cls(score, labels[:, sl].reshape(-1), label_w[:, sl].reshape(-1),
+                                            avg_factor=n_samples))
+            losses_bbox.append(self.loss_bbox(self._per_anchor(reg, 4).reshape(-1, 4), box_t[:, sl].reshape(-1, 4),
+                                              box_w[:, sl].reshape(-1, 4), avg_factor=n_samples))
+        return dict(loss_rpn_cls=losses_cls, loss_rpn_bbox=losses_bbox)
+
+    # ------------------------------------------------------------------ proposals (always nms_post rows)
+    def _image_proposals(self, level_scores, level_deltas, level_anchors, img_shape):
+        scores, deltas, anchors, ids = [], [], [], []
+        for lvl, (s, d, a) in enumerate(zip(level_scores, level_deltas, level_anchors)):
+            s = s.softmax(dim=1)[:, 1]
+            if self.nms_pre > 0 and s.shape[0] > self.nms_pre:
+                s, top = torch.topk(s, self.nms_pre)
+                d, a = d[top], a[top]
+            scores.append(s)
+            deltas.append(d)
+            anchors.append(a)
+            ids.append(torch.full((s.shape[0],), lvl, dtype=torch.long, device=s.device))
+        scores, ids = torch.cat(scores), torch.cat(ids)
+        boxes = self.bbox_coder.decode(torch.cat(anchors), torch.cat(deltas), max_shape=img_shape)
+        alive = torch.ones_like(scores, dtype=torch.bool)
+        if self.min_bbox_size >= 0:
+            alive = ((boxes[:, 2] - boxes[:, 0] > self.min_bbox_size) &
+                     (boxes[:, 3] - boxes[:, 1] > self.min_bbox_size))
+        return proposal_table(boxes, scores, ids, [int(x.shape[0]) for x in anchors], alive, self.nms_thresh, None,
+                              self.nms_post, invalid_score=INVALID_SCORE, global_nms=True)
+
+    def get_bboxes(self, cls_scores, bbox_preds, targets):
+        sizes = [tuple(c.shape[-2:]) for c in cls_scores]
+        level_anchors = self.anchor_generator.grid_anchors(sizes, device=cls_scores[0].device)
+        scores = [self._per_anchor(c.detach(), self.num_classes) for c in cls_scores]    # (N, H*W*A, 2) per level
+        deltas = [self._per_anchor(r.detach(), 4) for r in bbox_preds]
+        return [self._image_proposals([s[i] for s in scores], [d[i] for d in deltas], level_anchors,
+                                      target["img_size"]) for i, target in enumerate(targets)]
+
+    def forward(self, features, targets):
+        outs = run_levels(list(features), self.forward_single)
+        cls_scores, bbox_preds = [o[0] for o in outs], [o[1] for o in outs]
+        losses = self.loss(cls_scores, bbox_preds, targets) if self.training else dict()
+        return self.get_bboxes(cls_scores, bbox_preds, targets), losses
+
+    execute = forward
