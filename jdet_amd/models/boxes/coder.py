@@ -5,7 +5,8 @@ import math
 import torch
 
 from jdet_amd import _lib as L
-from jdet_amd.ops.bbox_transforms import hbb2poly, poly2hbb
+from jdet_amd.ops.bbox_transforms import (hbb2poly, obb2hbb, obb2poly, poly2hbb, rectpoly2obb, regular_obb,
+                                          regular_theta)
 from jdet_amd.utils.general import const_like
 from jdet_amd.utils.registry import BOXES
 
@@ -48,7 +49,6 @@ class MidpointOffsetCoder:
         self.stds = target_stds
 
     def encode(self, bboxes, gt_bboxes):
-        from jdet_amd.ops.bbox_transforms import obb2hbb, obb2poly
         assert bboxes.size(0) == gt_bboxes.size(0)
         if _fused_ok(bboxes, gt_bboxes) and bboxes.shape[1] == 4 and gt_bboxes.shape[1] == 5:
             a, g = L.f32c(bboxes), L.f32c(gt_bboxes)
@@ -88,8 +88,6 @@ class MidpointOffsetCoder:
         return (deltas - means) / stds
 
     def decode(self, bboxes, pred_bboxes, max_shape=None, wh_ratio_clip=16 / 1000):
-        import math
-        from jdet_amd.ops.bbox_transforms import rectpoly2obb
         assert pred_bboxes.size(0) == bboxes.size(0)
         if _fused_ok(bboxes, pred_bboxes) and bboxes.shape[1] == 4 and pred_bboxes.shape[1] == 6:
             a, d = L.f32c(bboxes), L.f32c(pred_bboxes)
@@ -137,8 +135,6 @@ class OrientedDeltaXYWHTCoder:
         self.stds = target_stds
 
     def encode(self, bboxes, gt_bboxes):
-        import math
-        from jdet_amd.ops.bbox_transforms import regular_theta
         assert bboxes.size(0) == gt_bboxes.size(0)
         assert bboxes.size(-1) == gt_bboxes.size(-1) == 5
         if _fused_ok(bboxes, gt_bboxes):
@@ -166,8 +162,6 @@ class OrientedDeltaXYWHTCoder:
         return (deltas - means) / stds
 
     def decode(self, bboxes, pred_bboxes, max_shape=None, wh_ratio_clip=16 / 1000):
-        import math
-        from jdet_amd.ops.bbox_transforms import regular_obb, regular_theta
         assert pred_bboxes.size(0) == bboxes.size(0)
         if _fused_ok(bboxes, pred_bboxes) and bboxes.shape[1] == 5 and pred_bboxes.shape[1] % 5 == 0:
             r, d = L.f32c(bboxes), L.f32c(pred_bboxes)

@@ -192,3 +192,42 @@ def sample_stage_rows(cands, alive, gts, gt_labels, assigner, sampler, dummy_box
     matched = torch.where(is_pos, gt_inds[rows] - 1, torch.zeros_like(rows))
     row_labels = torch.where(is_pos, labels[rows], torch.full_like(rows, background_label))
     return StageRows(sel, valid, is_pos, is_gt[rows] & valid, row_labels, matched)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# What every R-CNN stage does around its StageRows / proposal tables.
+
+# where dead rows (padding of a proposal table, unused sample rows) point: small boxes inside any image
+DUMMY_HBB = (4.0, 4.0, 12.0, 12.0)           # x1, y1, x2, y2
+DUMMY_OBB = (8.0, 8.0, 4.0, 4.0, 0.0)        # xc, yc, w, h, theta
+
+
+def with_image_index(per_image_boxes, first=0):
+    """boxes (n_i, D) of the images first, first + 1, ... -> rois (sum n_i, 1 + D) [image index, box]"""
+    return torch.cat([torch.cat([b.new_full((b.shape[0], 1), float(i)), b], dim=1)
+                      for i, b in enumerate(per_image_boxes, first)])
+
+
+def label_weights(valid, is_pos, pos_weight):
+    """classification weight of sampled rows: 0 off the valid rows, `pos_weight` on the positives (<= 0: 1) and 1 on
+    the negatives (bbox_head.py / rbbox_head.py `label_weights[:num_pos] = pos_weight`)"""
+    if pos_weight <= 0:
+        return valid.float()
+    return valid.float() * torch.where(is_pos, torch.full_like(valid, pos_weight, dtype=torch.float32),
+                                       torch.ones_like(valid, dtype=torch.float32))
+
+
+def class_rows(pred, labels, width, class_agnostic=False, num_classes=None):
+    """class-wise predictions (R, C * width) -> the (R, width) of each row's label; `num_classes`: labels are clamped
+    to num_classes - 1 first (heads whose background is the LAST class: its rows carry weight 0, any class will do)"""
+    if class_agnostic:
+        return pred.view(pred.size(0), width)
+    if num_classes is not None:
+        labels = labels.clamp(max=num_classes - 1)
+    return pred.view(pred.size(0), -1, width).gather(1, labels.long()[:, None, None].expand(-1, 1, width))[:, 0]
+
+
+def split_table(table, dummy_box):
+    """proposal table (P, D + 1) [box, score] -> (boxes (P, D) with the padding rows on `dummy_box`, alive (P,) bool)"""
+    alive = table[:, -1] >= 0
+    return torch.where(alive[:, None], table[:, :-1], dummy_box[None, :]), alive

@@ -4,7 +4,8 @@ per proposal) -> rotated RoIAlign on the enlarged RRoIs + head 1 (final rotated 
 import torch
 from torch import nn
 
-from jdet_amd.models.boxes.fixed_shape import sample_stage_rows
+from jdet_amd.models.boxes.fixed_shape import (DUMMY_HBB, DUMMY_OBB, sample_stage_rows, split_table,
+                                               with_image_index)
 from jdet_amd.ops.bbox_transforms import choose_best_Rroi_batch, dbbox2result, roi2droi
 from jdet_amd.utils.general import const_like
 from jdet_amd.utils.registry import BACKBONES, BOXES, HEADS, MODELS, NECKS, ROI_EXTRACTORS, build_from_cfg
@@ -42,11 +43,6 @@ class RoITransformer(nn.Module):
         assigner, sampler = getattr(self, key)
         return sample_stage_rows(cands, alive, gts, gt_labels, assigner, sampler, const_like(dummy, cands))
 
-    @staticmethod
-    def _with_image_index(per_image_boxes):
-        return torch.cat([torch.cat([b.new_full((b.shape[0], 1), float(i)), b], dim=1)
-                          for i, b in enumerate(per_image_boxes)])
-
     def execute_train(self, images, targets=None):
         """Two sampled R-CNN stages on fixed-size row sets: every image contributes exactly `sampler.num` rows per
         stage (padding rows have weight 0 everywhere), so the step has static shapes and never waits for the device
@@ -67,9 +63,9 @@ class RoITransformer(nn.Module):
         proposal_cfg = self.train_cfg.get("rpn_proposal", self.test_cfg["rpn"])
         with torch.no_grad():
             tables = self.rpn_head.get_bboxes(*rpn_outs, image_meta, proposal_cfg)
-            rows0 = [self._stage_rows(0, t[:, :4], t[:, 4] >= 0, g, l, (4.0, 4.0, 12.0, 12.0))
+            rows0 = [self._stage_rows(0, t[:, :4], t[:, 4] >= 0, g, l, DUMMY_HBB)
                      for t, g, l in zip(tables, gt_bboxes, gt_labels)]
-            rois = self._with_image_index([r.boxes for r in rows0])
+            rois = with_image_index([r.boxes for r in rows0])
         bbox_feats = self.bbox_roi_extractor(features[:self.bbox_roi_extractor.num_inputs], rois)
         cls_score, bbox_pred = self.bbox_head(bbox_feats)
         with torch.no_grad():
@@ -81,9 +77,9 @@ class RoITransformer(nn.Module):
             refined = self.bbox_head.refine_rbboxes(roi2droi(rois), rbbox_targets[0], bbox_pred.detach(), rows0,
                                                     image_meta)
             gt_best = [choose_best_Rroi_batch(g) for g in gt_obbs]
-            rows1 = [self._stage_rows(1, boxes, alive, g, l, (8.0, 8.0, 4.0, 4.0, 0.0))
+            rows1 = [self._stage_rows(1, boxes, alive, g, l, DUMMY_OBB)
                      for (boxes, alive), g, l in zip(refined, gt_best, gt_labels)]
-            rrois = self._enlarge(self._with_image_index([r.boxes for r in rows1]))
+            rrois = self._enlarge(with_image_index([r.boxes for r in rows1]))
         rbbox_feats = self.rbbox_roi_extractor(features[:self.rbbox_roi_extractor.num_inputs], rrois)
         cls_score, rbbox_pred = self.rbbox_head(rbbox_feats)
         with torch.no_grad():
@@ -108,10 +104,9 @@ class RoITransformer(nn.Module):
         tables = self.rpn_head.get_bboxes(*rpn_outs, img_meta, self.test_cfg["rpn"])
         results = []
         for i, table in enumerate(tables):       # the reference handles one image per call (img_meta[0], L176-178)
-            alive = table[:, 4] >= 0              # padding rows: pooled from a dummy box, scores zeroed below
-            boxes = torch.where(alive[:, None], table[:, :4], const_like((4.0, 4.0, 12.0, 12.0), table)[None, :])
-            rois = self._with_image_index([boxes])
-            rois[:, 0] = float(i)
+            # padding rows: pooled from a dummy box, scores zeroed below
+            boxes, alive = split_table(table, const_like(DUMMY_HBB, table))
+            rois = with_image_index([boxes], first=i)
             roi_feats = self.bbox_roi_extractor(x[:len(self.bbox_roi_extractor.featmap_strides)], rois)
             cls_score, bbox_pred = self.bbox_head(roi_feats)
             bbox_label = torch.argmax(cls_score, dim=1)

@@ -14,20 +14,15 @@ nonzero / boolean masks / randperm, L281-329 and anchor_target.py:L96-160):
 """
 import numpy as np
 import torch
-import torch.nn.functional as F
 from torch import nn
 
-from jdet_amd.ops.conv_igemm import conv_module
 from jdet_amd.models.boxes.anchor_target import anchor_inside_flags
 from jdet_amd.models.boxes.fixed_shape import dense_anchor_targets, proposal_table
-from jdet_amd.models.utils.level_pack import run_levels
-from jdet_amd.ops import conv_igemm
 from jdet_amd.ops.bbox_transforms import bbox2delta, delta2bbox
 from jdet_amd.utils.registry import BOXES, HEADS, LOSSES, build_from_cfg
 
+from . import _rpn_common as rpn
 from .anchor_generator import AnchorGenerator
-
-INVALID_SCORE = -1.0   # score of a padding row in a proposal table
 
 
 @HEADS.register_module()
@@ -68,8 +63,7 @@ class AnchorHead(nn.Module):
         return self.conv_cls(x), self.conv_reg(x)
 
     def forward(self, feats):
-        outs = run_levels(list(feats), self.forward_single)     # small levels as one packed tensor
-        return [o[0] for o in outs], [o[1] for o in outs]
+        return rpn.level_outputs(self, feats)
 
     execute = forward
 
@@ -86,11 +80,6 @@ class AnchorHead(nn.Module):
             vw = min(int(np.ceil(pad_shape[1] / stride)), fw)
             flags.append(g.valid_flags((fh, fw), (vh, vw), device))
         return torch.cat(flags)
-
-    @staticmethod
-    def _per_anchor(t, width):
-        """(N, A*width, H, W) -> (N, H*W*A, width): the anchor order of grid_anchors (location-major, A fastest)"""
-        return t.permute(0, 2, 3, 1).reshape(t.shape[0], -1, width)
 
     # ------------------------------------------------------------------ loss
     def loss(self, cls_scores, bbox_preds, gt_bboxes, gt_labels, img_metas, cfg, gt_bboxes_ignore=None):
@@ -112,48 +101,26 @@ class AnchorHead(nn.Module):
                                          meta["img_shape"][:2], cfg.get("allowed_border", -1))
             per_image.append(dense_anchor_targets(anchors, inside, gt, gt, assigner, sampler, encode, 4, 0,
                                                   cfg.get("pos_weight", -1)))
-        labels, label_w, box_t, box_w = (torch.stack([p[k] for p in per_image]) for k in range(4))
-        # sum over images of max(#pos, 1) + max(#neg, 1) (anchor_target.py:L77-78), kept on the device
-        n_samples = sum(torch.clamp(p[4], min=1) + torch.clamp(p[5], min=1) for p in per_image).float()
-        losses_cls, losses_bbox, start = [], [], 0
-        for cls, reg, lvl in zip(cls_scores, bbox_preds, per_level):
-            sl = slice(start, start + lvl.shape[0])
-            start += lvl.shape[0]
-            losses_cls.append(self.loss_cls(self._per_anchor(cls, 1).reshape(-1, 1), labels[:, sl].reshape(-1),
-                                            label_w[:, sl].reshape(-1), avg_factor=n_samples))
-            losses_bbox.append(self.loss_bbox(self._per_anchor(reg, 4).reshape(-1, 4), box_t[:, sl].reshape(-1, 4),
-                                              box_w[:, sl].reshape(-1, 4), avg_factor=n_samples))
+        losses_cls, losses_bbox = rpn.dense_loss(self, cls_scores, bbox_preds, per_level, per_image, 1, 4)
         return dict(loss_cls=losses_cls, loss_bbox=losses_bbox)
 
     # ------------------------------------------------------------------ proposals
-    def _image_proposals(self, level_scores, level_deltas, level_anchors, img_shape, cfg):
-        scores, boxes, ids, sizes = [], [], [], []
-        for lvl, (s, d, a) in enumerate(zip(level_scores, level_deltas, level_anchors)):
-            s = s.sigmoid() if self.use_sigmoid_cls else s.softmax(dim=1)[:, 1]
-            n = s.shape[0] if cfg["nms_pre"] <= 0 else min(cfg["nms_pre"], s.shape[0])
-            s, top = torch.topk(s, n)                          # descending; equal scores: lowest index first
-            scores.append(s)
-            boxes.append(delta2bbox(a[top], d[top], self.target_means, self.target_stds, img_shape))
-            ids.append(torch.full((n,), lvl, dtype=torch.long, device=s.device))
-            sizes.append(n)
-        scores, boxes, ids = torch.cat(scores), torch.cat(boxes), torch.cat(ids)
+    def _image_table(self, scores, deltas, anchors, ids, sizes, img_shape, cfg):
+        boxes = delta2bbox(anchors, deltas, self.target_means, self.target_stds, img_shape)
         alive = torch.ones_like(scores, dtype=torch.bool)
         if cfg["min_bbox_size"] > 0:
             alive = ((boxes[:, 2] - boxes[:, 0] + 1 >= cfg["min_bbox_size"]) &
                      (boxes[:, 3] - boxes[:, 1] + 1 >= cfg["min_bbox_size"]))
         return proposal_table(boxes, scores, ids, sizes, alive, cfg["nms_thr"], cfg["nms_post"], cfg["max_num"],
-                              nms_across_levels=cfg["nms_across_levels"], invalid_score=INVALID_SCORE)
+                              nms_across_levels=cfg["nms_across_levels"], invalid_score=rpn.INVALID_SCORE)
 
     def get_bboxes(self, cls_scores, bbox_preds, img_metas, cfg, rescale=False):
         """one (max_num, 5) proposal table per image"""
         assert len(cls_scores) == len(bbox_preds) and not rescale
-        width = 1 if self.use_sigmoid_cls else 2
         anchors = self.level_anchors([tuple(c.shape[-2:]) for c in cls_scores], cls_scores[0].device)
-        scores = [self._per_anchor(c.detach(), width) for c in cls_scores]
-        scores = [s[..., 0] if self.use_sigmoid_cls else s for s in scores]
-        deltas = [self._per_anchor(r.detach(), 4) for r in bbox_preds]
-        return [self._image_proposals([s[i] for s in scores], [d[i] for d in deltas], anchors, meta["img_shape"], cfg)
-                for i, meta in enumerate(img_metas)]
+        width, objectness = (1, rpn.sigmoid_objectness) if self.use_sigmoid_cls else (2, rpn.softmax_objectness)
+        cands = rpn.image_candidates(cls_scores, bbox_preds, anchors, width, 4, objectness, cfg["nms_pre"], True)
+        return [self._image_table(*c, meta["img_shape"], cfg) for c, meta in zip(cands, img_metas)]
 
 
 @HEADS.register_module()
@@ -169,9 +136,7 @@ class FasterrcnnHead(AnchorHead):
     def _heads(self):
         return [self.rpn_conv, self.rpn_cls, self.rpn_reg]
 
-    def forward_single(self, x, mask=None):
-        x = conv_igemm.conv3x3_module(self.rpn_conv, x, relu=True)      # the 1x1 layers below read no neighbours: a packed input needs no mask
-        return conv_module(self.rpn_cls, x), conv_module(self.rpn_reg, x)
+    forward_single = rpn.forward_single
 
     def loss(self, cls_scores, bbox_preds, gt_bboxes, img_metas, cfg, gt_bboxes_ignore=None):
         losses = super().loss(cls_scores, bbox_preds, gt_bboxes, None, img_metas, cfg,

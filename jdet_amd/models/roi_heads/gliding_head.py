@@ -30,7 +30,8 @@ import torch.nn.functional as F
 from torch import nn
 
 from jdet_amd.models.boxes.coder import gliding_decode, gliding_targets
-from jdet_amd.models.boxes.fixed_shape import sample_stage_rows
+from jdet_amd.models.boxes.fixed_shape import (DUMMY_HBB, class_rows, label_weights, sample_stage_rows, split_table,
+                                               with_image_index)
 from jdet_amd.ops.bbox_transforms import obb2poly
 from jdet_amd.ops.linear import Linear
 from jdet_amd.ops.nms_poly import multiclass_poly_nms
@@ -118,10 +119,6 @@ class GlidingHead(nn.Module):
 
     # ------------------------------------------------------------------ training
     @staticmethod
-    def _dummy_box(like):
-        return const_like([4.0, 4.0, 12.0, 12.0], like)
-
-    @staticmethod
     def gt_polys(target):
         """the gt polygons of one image: `target["polys"]`, or the corners of `target["rboxes"]` where the key is
         absent"""
@@ -133,7 +130,7 @@ class GlidingHead(nn.Module):
         (num, 8) [the polygon of gt 0 off the positives]"""
         gt_labels = (target["labels"] - 1).long()         # 0-based, background = num_classes (L394)
         rows = sample_stage_rows(table[:, :4], table[:, 4] >= 0, target["hboxes"], gt_labels, self.assigner,
-                                 self.sampler, self._dummy_box(table), background_label=self.num_classes)
+                                 self.sampler, const_like(DUMMY_HBB, table), background_label=self.num_classes)
         return rows, self.gt_polys(target)[rows.matched]
 
     def targets(self, per_image, fused=None):
@@ -145,20 +142,9 @@ class GlidingHead(nn.Module):
         pos = torch.cat([r.is_pos for r, _ in per_image])
         valid = torch.cat([r.valid for r, _ in per_image])
         labels = torch.cat([r.labels for r, _ in per_image])
-        pw = 1.0 if self.pos_weight <= 0 else self.pos_weight
-        label_weights = valid.float() * torch.where(pos, torch.full_like(valid, pw, dtype=torch.float32),
-                                                    torch.ones_like(valid, dtype=torch.float32))
         bbox_t, fix_t, ratio_t = gliding_targets(boxes, polys, self.bbox_coder.means, self.bbox_coder.stds, fused=fused)
         zero = lambda t: torch.where(pos[:, None], t, torch.zeros_like(t))   # noqa: E731
-        return labels, label_weights, zero(bbox_t), zero(fix_t), zero(ratio_t), pos, valid
-
-    def _class_rows(self, pred, labels, width):
-        """class-specific predictions (R, C*width) -> the (R, width) of each row's label (L231-238)"""
-        if self.reg_class_agnostic:
-            return pred.view(pred.size(0), width)
-        cls_of_row = labels.clamp(max=self.num_classes - 1)
-        pred = pred.view(pred.size(0), -1, width)
-        return pred.gather(1, cls_of_row[:, None, None].expand(-1, 1, width))[:, 0]
+        return labels, label_weights(valid, pos, self.pos_weight), zero(bbox_t), zero(fix_t), zero(ratio_t), pos, valid
 
     def loss(self, cls_score, bbox_pred, fix_pred, ratio_pred, labels, label_weights, bbox_targets, fix_targets,
              ratio_targets, pos, valid):
@@ -168,18 +154,20 @@ class GlidingHead(nn.Module):
         # positives only, normalised by the number of sampled rows (`bbox_targets.size(0)`, L240-281)
         n_rows = torch.clamp(valid.sum().float(), min=1.0)
         w = pos.float()[:, None]
-        losses["gliding_bbox_loss"] = self.bbox_loss(self._class_rows(bbox_pred, labels, 4), bbox_targets,
+
+        def of_label(pred, width):       # class-specific predictions (R, C*width) -> each row's (R, width), L231-238
+            return class_rows(pred, labels, width, self.reg_class_agnostic, self.num_classes)
+        losses["gliding_bbox_loss"] = self.bbox_loss(of_label(bbox_pred, 4), bbox_targets,
                                                      w.repeat(1, 4), avg_factor=n_rows)
-        losses["gliding_fix_loss"] = self.fix_loss(self._class_rows(fix_pred, labels, 4), fix_targets,
+        losses["gliding_fix_loss"] = self.fix_loss(of_label(fix_pred, 4), fix_targets,
                                                    w.repeat(1, 4), avg_factor=n_rows)
-        losses["gliding_ratio_loss"] = self.ratio_loss(self._class_rows(ratio_pred, labels, 1), ratio_targets,
+        losses["gliding_ratio_loss"] = self.ratio_loss(of_label(ratio_pred, 1), ratio_targets,
                                                        w.clone(), avg_factor=n_rows)
         return losses
 
     def forward_train(self, feats, proposal_tables, targets):
         per_image = [self.sample(t, tg) for t, tg in zip(proposal_tables, targets)]
-        rois = torch.cat([torch.cat([r.boxes.new_full((r.boxes.shape[0], 1), float(i)), r.boxes], dim=1)
-                          for i, (r, _) in enumerate(per_image)])
+        rois = with_image_index([r.boxes for r, _ in per_image])
         with torch.no_grad():
             tgt = self.targets(per_image)
         return self.loss(*self.forward_single(feats, rois), *tgt)
@@ -216,10 +204,8 @@ class GlidingHead(nn.Module):
     def forward_test(self, feats, proposal_tables, targets):
         results = []
         for i, (table, target) in enumerate(zip(proposal_tables, targets)):
-            alive = table[:, 4] >= 0
-            boxes = torch.where(alive[:, None], table[:, :4], self._dummy_box(table)[None, :])
-            rois = torch.cat([boxes.new_full((boxes.shape[0], 1), float(i)), boxes], dim=1)
-            cls_score, bbox_pred, fixes, ratios = self.forward_single(feats, rois)
+            boxes, alive = split_table(table, const_like(DUMMY_HBB, table))
+            cls_score, bbox_pred, fixes, ratios = self.forward_single(feats, with_image_index([boxes], first=i))
             dets, labels = self.get_bboxes(boxes, cls_score, bbox_pred, fixes, ratios, target["img_size"],
                                            target["scale_factor"], alive=alive)
             results.append((dets[:, :8], dets[:, 8], labels))

@@ -17,14 +17,11 @@ a proposal TABLE of exactly `nms_post` rows [x1, y1, x2, y2, score] sorted by sc
 import torch
 from torch import nn
 
-from jdet_amd.ops.conv_igemm import conv_module
 from jdet_amd.models.boxes.anchor_target import anchor_inside_flags
 from jdet_amd.models.boxes.fixed_shape import dense_anchor_targets, proposal_table
-from jdet_amd.models.utils.level_pack import run_levels
-from jdet_amd.ops import conv_igemm
 from jdet_amd.utils.registry import BOXES, HEADS, LOSSES, build_from_cfg
 
-INVALID_SCORE = -1.0   # score of a padding row in a proposal table
+from . import _rpn_common as rpn
 
 
 @HEADS.register_module()
@@ -57,17 +54,7 @@ class GlidingRPNHead(nn.Module):
         self.rpn_cls = nn.Conv2d(feat_channels, self.num_anchors * num_classes, 1)
         self.rpn_reg = nn.Conv2d(feat_channels, self.num_anchors * 4, 1)
 
-    # ------------------------------------------------------------------ network
-    def forward_single(self, x, mask=None):
-        """`mask` is part of `run_levels`' callback signature (the gap mask of a packed input); the 1x1 layers below
-        read no neighbours, so a packed input needs none here"""
-        x = conv_igemm.conv3x3_module(self.rpn_conv, x, relu=True)
-        return conv_module(self.rpn_cls, x), conv_module(self.rpn_reg, x)
-
-    @staticmethod
-    def _per_anchor(t, width):
-        """(N, A*width, H, W) -> (N, H*W*A, width): the anchor order of grid_anchors (location-major, A fastest)"""
-        return t.permute(0, 2, 3, 1).reshape(t.shape[0], -1, width)
+    forward_single = rpn.forward_single
 
     # ------------------------------------------------------------------ targets (dense over all anchors)
     def loss(self, cls_scores, bbox_preds, targets):
@@ -84,52 +71,30 @@ class GlidingRPNHead(nn.Module):
             # label 1 on the sampled positives, 0 elsewhere (L250-261); pos_weight is fixed at 1 there
             per_image.append(dense_anchor_targets(anchors, inside, gt, gt, self.assigner, self.sampler,
                                                   self.bbox_coder.encode, 4, 0, -1))
-        labels, label_w, box_t, box_w = (torch.stack([p[k] for p in per_image]) for k in range(4))
-        # sum over images of max(#pos, 1) + max(#neg, 1)  (L292-293, L364), kept on the device
-        n_samples = sum(torch.clamp(p[4], min=1) + torch.clamp(p[5], min=1) for p in per_image).float()
-        losses_cls, losses_bbox, start = [], [], 0
-        for cls, reg, lvl in zip(cls_scores, bbox_preds, level_anchors):
-            sl = slice(start, start + lvl.shape[0])
-            start += lvl.shape[0]
-            score = self._per_anchor(cls, self.num_classes).reshape(-1, self.num_classes)
-            losses_cls.append(self.loss_cls(score, labels[:, sl].reshape(-1), label_w[:, sl].reshape(-1),
-                                            avg_factor=n_samples))
-            losses_bbox.append(self.loss_bbox(self._per_anchor(reg, 4).reshape(-1, 4), box_t[:, sl].reshape(-1, 4),
-                                              box_w[:, sl].reshape(-1, 4), avg_factor=n_samples))
+        losses_cls, losses_bbox = rpn.dense_loss(self, cls_scores, bbox_preds, level_anchors, per_image,
+                                                 self.num_classes, 4)
         return dict(loss_rpn_cls=losses_cls, loss_rpn_bbox=losses_bbox)
 
     # ------------------------------------------------------------------ proposals (always nms_post rows)
-    def _image_proposals(self, level_scores, level_deltas, level_anchors, img_shape):
-        scores, deltas, anchors, ids = [], [], [], []
-        for lvl, (s, d, a) in enumerate(zip(level_scores, level_deltas, level_anchors)):
-            s = s.softmax(dim=1)[:, 1]
-            if self.nms_pre > 0 and s.shape[0] > self.nms_pre:
-                s, top = torch.topk(s, self.nms_pre)
-                d, a = d[top], a[top]
-            scores.append(s)
-            deltas.append(d)
-            anchors.append(a)
-            ids.append(torch.full((s.shape[0],), lvl, dtype=torch.long, device=s.device))
-        scores, ids = torch.cat(scores), torch.cat(ids)
-        boxes = self.bbox_coder.decode(torch.cat(anchors), torch.cat(deltas), max_shape=img_shape)
+    def _image_table(self, scores, deltas, anchors, ids, sizes, img_shape):
+        boxes = self.bbox_coder.decode(anchors, deltas, max_shape=img_shape)
         alive = torch.ones_like(scores, dtype=torch.bool)
         if self.min_bbox_size >= 0:
             alive = ((boxes[:, 2] - boxes[:, 0] > self.min_bbox_size) &
                      (boxes[:, 3] - boxes[:, 1] > self.min_bbox_size))
-        return proposal_table(boxes, scores, ids, [int(x.shape[0]) for x in anchors], alive, self.nms_thresh, None,
-                              self.nms_post, invalid_score=INVALID_SCORE, global_nms=True)
+        return proposal_table(boxes, scores, ids, sizes, alive, self.nms_thresh, None, self.nms_post,
+                              invalid_score=rpn.INVALID_SCORE, global_nms=True)
 
     def get_bboxes(self, cls_scores, bbox_preds, targets):
         sizes = [tuple(c.shape[-2:]) for c in cls_scores]
         level_anchors = self.anchor_generator.grid_anchors(sizes, device=cls_scores[0].device)
-        scores = [self._per_anchor(c.detach(), self.num_classes) for c in cls_scores]    # (N, H*W*A, 2) per level
-        deltas = [self._per_anchor(r.detach(), 4) for r in bbox_preds]
-        return [self._image_proposals([s[i] for s in scores], [d[i] for d in deltas], level_anchors,
-                                      target["img_size"]) for i, target in enumerate(targets)]
+        # no top-k on a level that keeps all its anchors: the global NMS visits by a stable argsort of its own
+        cands = rpn.image_candidates(cls_scores, bbox_preds, level_anchors, self.num_classes, 4,
+                                     rpn.softmax_objectness, self.nms_pre, False)
+        return [self._image_table(*c, target["img_size"]) for c, target in zip(cands, targets)]
 
     def forward(self, features, targets):
-        outs = run_levels(list(features), self.forward_single)
-        cls_scores, bbox_preds = [o[0] for o in outs], [o[1] for o in outs]
+        cls_scores, bbox_preds = rpn.level_outputs(self, features)
         losses = self.loss(cls_scores, bbox_preds, targets) if self.training else dict()
         return self.get_bboxes(cls_scores, bbox_preds, targets), losses
 

@@ -21,7 +21,8 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from jdet_amd.models.boxes.fixed_shape import sample_rows
+from jdet_amd.models.boxes.fixed_shape import (DUMMY_OBB, class_rows, label_weights, sample_stage_rows, split_table,
+                                               with_image_index)
 from jdet_amd.models.utils.modules import ConvModule
 from jdet_amd.ops.bbox_transforms import get_bbox_dim, obb2poly
 from jdet_amd.utils.general import const_like
@@ -127,58 +128,39 @@ class OrientedHead(nn.Module):
         return outs
 
     # ------------------------------------------------------------------ training
-    @staticmethod
-    def _dummy_box(like):
-        return const_like([8.0, 8.0, 4.0, 4.0, 0.0], like)
-
-    def _image_samples(self, table, target):
-        """proposal table (P, 6) of one image -> the image's `num` sampled rows:
-        boxes (num,5), labels (num,) long, label_weights (num,), bbox_targets (num,5), bbox_weights (num,5)"""
+    def sample(self, table, target):
+        """proposal table (P, 6) of one image -> its `num` sampled rows (StageRows) and their matched gts (num, 5)
+        [gt 0 off the positives]"""
         gt = target["rboxes"].clone()
         gt[:, -1] *= -1                                   # Oriented R-CNN angle convention (L459-466)
         gt_labels = (target["labels"] - 1).long()         # 0-based, background = num_classes (L472)
-        boxes, alive = table[:, :5], table[:, 5] >= 0
-        overlaps = self.assigner.iou_calculator(gt, boxes)
-        overlaps = torch.where(alive[None, :], overlaps, torch.full_like(overlaps, -1.0))   # padding rows: ignored
-        assign = self.assigner.assign_wrt_overlaps(overlaps, gt_labels)
-        gt_inds, labels = assign.gt_inds.long(), assign.labels.long()
-        s = self.sampler
-        if s.add_gt_as_proposals:                          # the gts join the candidates, matched to themselves (L92-99)
-            k = gt.shape[0]
-            boxes = torch.cat([gt, boxes])
-            gt_inds = torch.cat([torch.arange(1, k + 1, device=gt.device), gt_inds])
-            labels = torch.cat([gt_labels, labels])
-        rows, valid, is_pos = sample_rows(gt_inds, s.num, s.pos_fraction, s.neg_pos_ub)
-        sel = torch.where(valid[:, None], boxes[rows], self._dummy_box(boxes)[None, :])
-        matched = gt[(gt_inds[rows] - 1).clamp(min=0)]
-        bg = torch.full_like(rows, self.num_classes)
-        out_labels = torch.where(is_pos, labels[rows], bg)
-        pw = 1.0 if self.pos_weight <= 0 else self.pos_weight
-        label_weights = valid.float() * torch.where(is_pos, torch.full_like(valid, pw, dtype=torch.float32),
-                                                    torch.ones_like(valid, dtype=torch.float32))
-        bbox_targets = self.bbox_coder.encode(sel, matched)
-        bbox_weights = is_pos.float()[:, None].expand(-1, self.reg_dim)
-        bbox_targets = torch.where(is_pos[:, None], bbox_targets, torch.zeros_like(bbox_targets))
-        return sel, out_labels, label_weights, bbox_targets, bbox_weights, valid
+        rows = sample_stage_rows(table[:, :5], table[:, 5] >= 0, gt, gt_labels, self.assigner, self.sampler,
+                                 const_like(DUMMY_OBB, table), background_label=self.num_classes)
+        return rows, gt[rows.matched]
+
+    def targets(self, per_image):
+        """[(StageRows, matched gts)] -> labels (R,) long, label_weights (R,), bbox_targets (R,5), bbox_weights (R,5),
+        valid (R,) bool over the R = images * num rows; one encode for the rows of all images"""
+        boxes = torch.cat([r.boxes for r, _ in per_image])
+        pos = torch.cat([r.is_pos for r, _ in per_image])
+        valid = torch.cat([r.valid for r, _ in per_image])
+        labels = torch.cat([r.labels for r, _ in per_image])
+        bbox_targets = self.bbox_coder.encode(boxes, torch.cat([g for _, g in per_image]))
+        bbox_targets = torch.where(pos[:, None], bbox_targets, torch.zeros_like(bbox_targets))
+        return (labels, label_weights(valid, pos, self.pos_weight), bbox_targets,
+                pos.float()[:, None].repeat(1, self.reg_dim), valid)
 
     def forward_train(self, feats, proposal_tables, targets):
-        per_image = [self._image_samples(t, tg) for t, tg in zip(proposal_tables, targets)]
-        rois = torch.cat([torch.cat([b.new_full((b.shape[0], 1), float(i)), b], dim=1)
-                          for i, (b, *_rest) in enumerate(per_image)])
-        labels, label_w, box_t, box_w, valid = (torch.cat([p[k] for p in per_image]) for k in range(1, 6))
-        cls_score, bbox_pred = self._trunk(feats, rois)
+        per_image = [self.sample(t, tg) for t, tg in zip(proposal_tables, targets)]
+        labels, label_w, box_t, box_w, valid = self.targets(per_image)
+        cls_score, bbox_pred = self._trunk(feats, with_image_index([r.boxes for r, _ in per_image]))
         n_rows = valid.sum().float()
         losses = dict()
         # classification: mean over the sampled rows (L318-325); regression: positives only, normalised by the
         # number of sampled rows (L326-343) -- both as weighted sums over the fixed-size row set
         losses["loss_cls"] = self.loss_cls(cls_score, labels, label_w,
                                            avg_factor=torch.clamp((label_w > 0).sum().float(), min=1.0))
-        if self.reg_class_agnostic:
-            pred = bbox_pred.view(bbox_pred.size(0), self.reg_dim)
-        else:
-            cls_of_row = labels.clamp(max=self.num_classes - 1)
-            pred = bbox_pred.view(bbox_pred.size(0), -1, self.reg_dim)
-            pred = pred.gather(1, cls_of_row[:, None, None].expand(-1, 1, self.reg_dim))[:, 0]
+        pred = class_rows(bbox_pred, labels, self.reg_dim, self.reg_class_agnostic, self.num_classes)
         losses["orcnn_bbox_loss"] = self.loss_bbox(pred, box_t, box_w, avg_factor=torch.clamp(n_rows, min=1.0))
         return losses
 
@@ -200,10 +182,8 @@ class OrientedHead(nn.Module):
     def forward_test(self, feats, proposal_tables, targets):
         results = []
         for i, (table, target) in enumerate(zip(proposal_tables, targets)):
-            alive = table[:, 5] >= 0
-            boxes = torch.where(alive[:, None], table[:, :5], self._dummy_box(table)[None, :])
-            rois = torch.cat([boxes.new_full((boxes.shape[0], 1), float(i)), boxes], dim=1)
-            cls_score, bbox_pred = self._trunk(feats, rois)
+            boxes, alive = split_table(table, const_like(DUMMY_OBB, table))
+            cls_score, bbox_pred = self._trunk(feats, with_image_index([boxes], first=i))
             scores = F.softmax(cls_score, dim=1) * alive[:, None].float()       # padding rows score 0 everywhere
             decoded = self.bbox_coder.decode(boxes, bbox_pred, max_shape=target["img_size"])
             sf = target["scale_factor"]

@@ -18,18 +18,15 @@ number of gts:
     survivors of NMS carry score -1 (consumers ignore them).  No boolean indexing, no `.all()` / `.any()`.
 """
 import torch
-import torch.nn.functional as F
 from torch import nn
 
-from jdet_amd.ops.conv_igemm import conv_module
 from jdet_amd.models.boxes.anchor_target import anchor_inside_flags
 from jdet_amd.models.boxes.fixed_shape import dense_anchor_targets, proposal_table
-from jdet_amd.models.utils.level_pack import run_levels
-from jdet_amd.ops import conv_igemm
 from jdet_amd.ops.bbox_transforms import obb2hbb
 from jdet_amd.utils.registry import BOXES, HEADS, LOSSES, build_from_cfg
 
-INVALID_SCORE = -1.0   # score of a padding row in a proposal table
+from . import _rpn_common as rpn
+from ._rpn_common import INVALID_SCORE
 
 
 @HEADS.register_module()
@@ -66,16 +63,7 @@ class OrientedRPNHead(nn.Module):
         self.rpn_cls = nn.Conv2d(feat_channels, self.num_anchors * num_classes, 1)
         self.rpn_reg = nn.Conv2d(feat_channels, self.num_anchors * 6, 1)
 
-    # ------------------------------------------------------------------ network
-    def forward_single(self, x, mask=None):
-        x = conv_igemm.conv3x3_module(self.rpn_conv, x, relu=True)      # the 1x1 layers below read no neighbours: a packed input needs no mask
-        return conv_module(self.rpn_cls, x), conv_module(self.rpn_reg, x)
-
-    @staticmethod
-    def _per_anchor(t, width):
-        """(N, A*width, H, W) -> (N, H*W*A, width): the anchor order of grid_anchors (location-major, A fastest)"""
-        n = t.shape[0]
-        return t.permute(0, 2, 3, 1).reshape(n, -1, width)
+    forward_single = rpn.forward_single
 
     # ------------------------------------------------------------------ targets (dense over all anchors)
     def _image_targets(self, anchors, inside, target):
@@ -97,54 +85,28 @@ class OrientedRPNHead(nn.Module):
             valid = torch.cat(self.anchor_generator.valid_flags(sizes, target["pad_shape"], device=dev))
             inside = anchor_inside_flags(anchors, valid, target["img_size"][:2], allowed_border=0)
             per_image.append(self._image_targets(anchors, inside, target))
-        labels, label_w, box_t, box_w = (torch.stack([p[k] for p in per_image]) for k in range(4))
-        # sum over images of max(#pos, 1) + max(#neg, 1)  (L376-378), kept on the device
-        n_samples = sum(torch.clamp(p[4], min=1) + torch.clamp(p[5], min=1) for p in per_image).float()
-        losses_cls, losses_bbox = [], []
-        start = 0
-        for cls, reg, lvl in zip(cls_scores, bbox_preds, level_anchors):
-            n = lvl.shape[0]
-            sl = slice(start, start + n)
-            start += n
-            score = self._per_anchor(cls, self.cls_out_channels).reshape(-1, self.cls_out_channels)
-            losses_cls.append(self.loss_cls(score, labels[:, sl].reshape(-1), label_w[:, sl].reshape(-1),
-                                            avg_factor=n_samples))
-            pred = self._per_anchor(reg, self.reg_dim).reshape(-1, self.reg_dim)
-            losses_bbox.append(self.loss_bbox(pred, box_t[:, sl].reshape(-1, self.reg_dim),
-                                              box_w[:, sl].reshape(-1, self.reg_dim), avg_factor=n_samples))
+        losses_cls, losses_bbox = rpn.dense_loss(self, cls_scores, bbox_preds, level_anchors, per_image,
+                                                 self.cls_out_channels, self.reg_dim)
         return dict(loss_rpn_cls=losses_cls, loss_rpn_bbox=losses_bbox)
 
     # ------------------------------------------------------------------ proposals (always nms_post rows)
-    def _image_proposals(self, level_scores, level_deltas, level_anchors, img_shape):
-        scores, deltas, anchors, ids = [], [], [], []
-        for lvl, (s, d, a) in enumerate(zip(level_scores, level_deltas, level_anchors)):
-            s = s.sigmoid()
-            k = s.shape[0] if self.nms_pre <= 0 else min(self.nms_pre, s.shape[0])
-            s, top = torch.topk(s, k)         # always: proposal_table wants every level sorted by descending score
-            d, a = d[top], a[top]
-            scores.append(s)
-            deltas.append(d)
-            anchors.append(a)
-            ids.append(torch.full((s.shape[0],), lvl, dtype=torch.long, device=s.device))
-        scores, ids = torch.cat(scores), torch.cat(ids)
-        boxes = self.bbox_coder.decode(torch.cat(anchors), torch.cat(deltas), max_shape=img_shape)
+    def _image_table(self, scores, deltas, anchors, ids, sizes, img_shape):
+        boxes = self.bbox_coder.decode(anchors, deltas, max_shape=img_shape)
         alive = torch.ones_like(scores, dtype=torch.bool)
         if self.min_bbox_size >= 0:
             alive = (boxes[:, 2] > self.min_bbox_size) & (boxes[:, 3] > self.min_bbox_size)
-        return proposal_table(obb2hbb(boxes), scores, ids, [int(x.shape[0]) for x in anchors], alive, self.nms_thresh,
-                              None, self.nms_post, invalid_score=INVALID_SCORE, payload=boxes)
+        return proposal_table(obb2hbb(boxes), scores, ids, sizes, alive, self.nms_thresh, None, self.nms_post,
+                              invalid_score=INVALID_SCORE, payload=boxes)
 
     def get_bboxes(self, cls_scores, bbox_preds, targets):
         sizes = [tuple(c.shape[-2:]) for c in cls_scores]
         level_anchors = self.anchor_generator.grid_anchors(sizes, device=cls_scores[0].device)
-        scores = [self._per_anchor(c.detach(), 1)[..., 0] for c in cls_scores]          # (N, H*W*A) per level
-        deltas = [self._per_anchor(r.detach(), self.reg_dim) for r in bbox_preds]
-        return [self._image_proposals([s[i] for s in scores], [d[i] for d in deltas], level_anchors,
-                                      target["img_size"]) for i, target in enumerate(targets)]
+        cands = rpn.image_candidates(cls_scores, bbox_preds, level_anchors, 1, self.reg_dim, rpn.sigmoid_objectness,
+                                     self.nms_pre, True)
+        return [self._image_table(*c, target["img_size"]) for c, target in zip(cands, targets)]
 
     def forward(self, features, targets):
-        outs = run_levels(list(features), self.forward_single)
-        cls_scores, bbox_preds = [o[0] for o in outs], [o[1] for o in outs]
+        cls_scores, bbox_preds = rpn.level_outputs(self, features)
         losses = self.loss(cls_scores, bbox_preds, targets) if self.training else dict()
         return self.get_bboxes(cls_scores, bbox_preds, targets), losses
 

@@ -191,3 +191,107 @@ def test_subclass_hooks_and_compatibility_surface():
         SimpleNamespace(gt_inds=torch.tensor([1]), labels=None, add_gt_=lambda labels: None), torch.tensor([1., 2., 3., 4.]),
         torch.tensor([[1., 2., 3., 4.]]))
     assert one.pos_inds.tolist() == [0]
+
+
+# ------------------------------------------------------------------------- what the R-CNN stages share (fixed_shape.py)
+def test_with_image_index_two_images():
+    from jdet_amd.models.boxes.fixed_shape import with_image_index
+    a = torch.tensor([[1., 2., 3., 4.], [5., 6., 7., 8.]])
+    b = torch.tensor([[9., 10., 11., 12.]])
+    want = torch.tensor([[0., 1., 2., 3., 4.], [0., 5., 6., 7., 8.], [1., 9., 10., 11., 12.]])
+    assert torch.equal(with_image_index([a, b]), want)
+    assert torch.equal(with_image_index([b], first=3), torch.tensor([[3., 9., 10., 11., 12.]]))
+
+
+def test_label_weights_positive_negative_invalid_rows():
+    from jdet_amd.models.boxes.fixed_shape import label_weights
+    valid = torch.tensor([True, True, True, True, False, False])      # 2 positives, 2 negatives, 2 unused rows
+    is_pos = torch.tensor([True, True, False, False, False, False])
+    assert torch.equal(label_weights(valid, is_pos, -1), torch.tensor([1., 1., 1., 1., 0., 0.]))
+    assert torch.equal(label_weights(valid, is_pos, 2.0), torch.tensor([2., 2., 1., 1., 0., 0.]))
+    assert label_weights(valid, is_pos, -1).dtype == label_weights(valid, is_pos, 2.0).dtype == torch.float32
+
+
+def test_class_rows_widths_clamp_and_agnostic():
+    from jdet_amd.models.boxes.fixed_shape import class_rows
+    C = 3
+    labels = torch.tensor([0, 2, 1, 3])                     # the last row carries the background label C
+    for width in (4, 1):
+        pred = torch.arange(4 * C * width, dtype=torch.float32).view(4, C * width)
+        by_class = pred.view(4, C, width)
+        got = class_rows(pred, labels, width, num_classes=C)          # background -> the last class
+        assert got.shape == (4, width)
+        assert torch.equal(got, torch.stack([by_class[0, 0], by_class[1, 2], by_class[2, 1], by_class[3, 2]]))
+        # without the clamp the labels index the classes as they are (background is class 0 in those heads)
+        assert torch.equal(class_rows(pred[:3], labels[:3], width), got[:3])
+        with pytest.raises(RuntimeError):
+            class_rows(pred, labels, width)                            # label C is out of range: nothing is clamped
+        flat = pred[:, :width]
+        assert torch.equal(class_rows(flat, labels, width, class_agnostic=True), flat)
+
+
+def test_split_table_puts_padding_rows_on_the_dummy_box():
+    from jdet_amd.models.boxes.fixed_shape import DUMMY_HBB, split_table
+    table = torch.tensor([[10., 20., 30., 40., 0.9], [1., 2., 3., 4., 0.0], [0., 0., 0., 0., -1.], [0., 0., 0., 0., -1.]])
+    boxes, alive = split_table(table, torch.tensor(DUMMY_HBB))
+    assert alive.tolist() == [True, True, False, False]                # score 0 is a real row, score -1 is padding
+    assert torch.equal(boxes, torch.tensor([[10., 20., 30., 40.], [1., 2., 3., 4.], list(DUMMY_HBB), list(DUMMY_HBB)]))
+
+
+class _FixedOverlapAssigner:
+    """stand-in for MaxIoUAssigner + rotated IoU (both device-only): a fixed overlap matrix, positives at >= 0.5"""
+
+    def __init__(self, overlaps):
+        self.overlaps = overlaps
+
+    def iou_calculator(self, gts, boxes):
+        return self.overlaps
+
+    def assign_wrt_overlaps(self, overlaps, gt_labels):
+        from types import SimpleNamespace
+        best, arg = overlaps.max(dim=0)
+        gt_inds = torch.where(best >= 0.5, arg + 1, torch.zeros_like(arg))
+        gt_inds = torch.where(best < 0, torch.full_like(arg, -1), gt_inds)          # masked columns: ignored
+        return SimpleNamespace(gt_inds=gt_inds, labels=torch.where(gt_inds > 0, gt_labels[arg], torch.zeros_like(arg)))
+
+
+def test_oriented_head_targets_are_sample_stage_rows_plus_encode():
+    """OrientedHead's training rows = `sample_stage_rows` on the proposal table (gts in the head's negated-angle
+    convention, 0-based labels, background = num_classes) + `bbox_coder.encode`, under the same seed"""
+    import jdet_amd.models  # noqa: F401
+    from jdet_amd.models.boxes.fixed_shape import DUMMY_OBB, sample_stage_rows
+    from jdet_amd.models.roi_heads.oriented_head import OrientedHead
+    g = torch.Generator().manual_seed(7)
+    P, K, PAD = 1000, 7, 40
+
+    def boxes(n):
+        return torch.cat([torch.rand(n, 2, generator=g) * 500, torch.rand(n, 2, generator=g) * 80 + 10,
+                          torch.rand(n, 1, generator=g) * 3.0 - 1.5], 1)
+    table = torch.cat([torch.cat([boxes(P), torch.rand(P, 1, generator=g)], 1),
+                       torch.cat([torch.zeros(PAD, 5), -torch.ones(PAD, 1)], 1)])
+    target = dict(rboxes=boxes(K), labels=torch.randint(1, 16, (K,), generator=g))
+    overlaps = torch.rand(K, P + PAD, generator=g) * 0.45
+    hits = torch.randperm(P, generator=g)[:21]
+    overlaps[torch.arange(21) % K, hits] = 0.5 + torch.rand(21, generator=g) * 0.4
+    head = OrientedHead(num_classes=15, in_channels=8, fc_out_channels=16)
+    head.assigner = _FixedOverlapAssigner(overlaps)
+
+    torch.manual_seed(3)
+    sampled = head.sample(table, target)
+    labels, label_w, box_t, box_w, valid = head.targets([sampled])
+
+    torch.manual_seed(3)
+    gt = target["rboxes"].clone()
+    gt[:, -1] *= -1
+    rows = sample_stage_rows(table[:, :5], table[:, 5] >= 0, gt, target["labels"] - 1, head.assigner, head.sampler,
+                             torch.tensor(DUMMY_OBB), background_label=15)
+    n_pos = int(rows.is_pos.sum())
+    assert 3 <= n_pos < 128 and int(rows.valid.sum()) == 512        # both branches of the sampler have work
+    deltas = head.bbox_coder.encode(rows.boxes, gt[rows.matched])
+    assert torch.equal(sampled[0].boxes, rows.boxes) and torch.equal(sampled[1], gt[rows.matched])
+    assert torch.equal(labels, rows.labels) and torch.equal(valid, rows.valid)
+    assert torch.equal(label_w, rows.valid.float())
+    assert torch.equal(box_t, torch.where(rows.is_pos[:, None], deltas, torch.zeros_like(deltas)))
+    assert torch.equal(box_w, rows.is_pos.float()[:, None].expand(-1, 5))
+    assert bool((labels[rows.is_pos] < 15).all()) and bool((labels[~rows.is_pos] == 15).all())
+    assert float(box_t[rows.is_pos].abs().sum()) > 0 and float(box_t[~rows.is_pos].abs().sum()) == 0
