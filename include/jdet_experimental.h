@@ -63,6 +63,16 @@ int jdet_roi_align_forward_cl_mode(int mode, int variant, const float* feat_nhwc
                                    int n_orient, const int32_t* order, float* out_cl, void* workspace,
                                    size_t workspace_bytes, jdet_stream_t stream);
 
+/* The profiling build of the conv_bn kernel (csrc/experimental/conv_bn_stamps.hip: the product's csrc/conv_bn_kernel.h with
+ * its workgroup time stamps compiled in; scripts/r6_conv_stamps.py).  Arguments as jdet_conv_bn_forward's, without tile
+ * and workspace: always the 64 x 64 tile with 32-deep K steps, one wave group and operand tiles two steps ahead.  Every
+ * workgroup overwrites the first 16 floats of its tile's first output row: words 0-7 four 64-bit wall_clock64() stamps
+ * (start, K loop entered, K loop left, end), 8 HW_ID, 9 XCC_ID, 10 the workgroup id, 11 the mark 0x5741, 12-14 three
+ * intervals of the prologue / epilogue in ticks, 15 zero; every other output value is the product kernel's.
+ * JDET_E_UNSUPPORTED unless Cin % 32 == 0 and jdet_conv_bn_forward's own support and size limits hold. */
+int jdet_conv_bn_forward_stamps(const float* x_nhwc, int N, int H, int W, int Cin, const float* w_krsc, int Cout, int R,
+                                int stride, const jdet_conv_epilogue_t* epilogue, float* y_nhwc, jdet_stream_t stream);
+
 /* Calibration probe (scripts/gather_probe.py; csrc/experimental/gather_probe.hip): n_blocks workgroups of 4 waves, every
  * wave loads rows_per_wave pseudo-random 1 KiB rows of buf (total_rows x 256 floats), `unroll` (4 / 8 / 16) in flight,
  * drawn from a window of window_rows rows -- one shared window, or one per workgroup (local_windows != 0). */

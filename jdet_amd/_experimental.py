@@ -15,6 +15,7 @@ SIGNATURES = {
     "jdet_roi_align_forward_pool": (_i, [_i, _p, _i, _i, _i, _i, _p, _i, _i, _i, _f, _i, _p, _p, _sz, _p]),
     "jdet_roi_align_forward_cl_mode_workspace": (_sz, [_i] * 4),
     "jdet_roi_align_forward_cl_mode": (_i, [_i, _i, _p, _i, _i, _i, _i, _p, _i, _i, _i, _f, _i, _i, _p, _p, _p, _sz, _p]),
+    "jdet_conv_bn_forward_stamps": (_i, [_p, _i, _i, _i, _i, _p, _i, _i, _i, _p, _p, _p]),
     "jdet_debug_gather_probe": (_i, [_p, ctypes.c_long, _i, _i, _i, _i, _i, _p, _p]),
     "jdet_debug_gather_width_probe": (_i, [_p, ctypes.c_long, _i, _i, _i, _i, _p, _p]),
     "jdet_debug_gather_accumulate_probe": (_i, [_p, ctypes.c_long, _i, _i, _i, _i, _p, _p]),

@@ -32,15 +32,9 @@
 //     rows (incl. the halo shared by neighbouring tiles) of a band stay in one L2.
 //   * epilogue in registers: + bias, ReLU, x per-position mask (the gap rows of a LevelPack), 128-byte row segments.
 // The matrix pipe is the bound: 2 * M * N * K flop at 157 TFLOP/s (fp32-input MFMA = the fp32 vector rate).
-#include <cstdlib>
-
-#include "common.h"
+#include "conv_mfma.h"
 
 namespace {
-
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef unsigned v4u __attribute__((ext_vector_type(4)));
-typedef float v16f __attribute__((ext_vector_type(16)));
 
 struct ConvArgs {
   const float* x;        // (N, H, W, Cin)
@@ -53,42 +47,23 @@ struct ConvArgs {
   int N, H, W, Cin, Cout, relu, ksplit;
 };
 
-constexpr unsigned kOob = 0xFFFFFFF0u;   // a byte offset past every buffer: the load returns zeros
 
-__device__ __forceinline__ v4f buf_load(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-  return __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
-}
-
-// byte position of chunk (4 floats) `chunk` of LDS row `row` (see header)
-template <int BK>
-__device__ __forceinline__ int swz_bytes(int row, int chunk) {
-  return (row * BK + ((chunk ^ (BK == 16 ? (row >> 2) & 3 : (row >> 1) & 7)) << 2)) * 4;
-}
-
-// DEPTH = 2 (round 6; 64 x 64 tiles, one wave group, plain taps): operand tiles requested TWO K steps ahead into two
-// register sets -- see conv_bn.hip: a 64 x 64 tile's K step is 0.43 us of MFMAs per wave, less than a global round trip.
-template <int BT, int BK, int KG, bool DEFORM, int DEPTH = 1>
+template <int BT, int BK, int KG, bool DEFORM>
 __global__ __launch_bounds__(256 * KG)
 __attribute__((amdgpu_waves_per_eu(BT == 128 ? (KG == 2 ? 4 : (BK == 32 ? 2 : (DEFORM ? 3 : 4))) : 4)))
 void conv3x3_igemm_kernel(ConvArgs a) {
-  constexpr int NTHR = 256 * KG;
-  constexpr int T = BT / 64;             // 32 x 32 tiles per wave and direction
-  constexpr int CH = BK / 4;             // 16-byte chunks per LDS row
-  constexpr int RPP = NTHR / CH;         // loader: RPP rows x CH chunks per pass
-  constexpr int PASSES = BT / RPP;
+  using TL = MfmaTile<BT, BK, KG>;
+  constexpr int T = TL::T, CH = TL::CH, RPP = TL::RPP, PASSES = TL::PASSES, TILE = TL::TILE, QN = TL::QN;
   constexpr int NC = DEFORM ? 4 : 1;
-  constexpr int TILE = BT * BK * 4;      // bytes of one operand tile
-  constexpr int QN = BK / 8 / KG;        // 8-deep slices per wave and K step
-  static_assert(PASSES >= 1 && QN >= 1, "tile shape");
+  // operand tiles TWO K steps ahead into two register sets (conv_mfma_loop.inc): the 64 x 64 tile with one wave group and
+  // plain taps (the gather's bilinear weights belong to the loads in flight)
+  constexpr int DEPTH = (BT == 64 && KG == 1 && !DEFORM) ? 2 : 1;
   __shared__ __attribute__((aligned(16))) char s_raw[4 * TILE];     // [buffer][A | B]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const long M = (long)a.N * a.H * a.W;
-  // ---- XCD-aware tile id ----
   const int NT = (a.Cout + BT - 1) / BT;
-  const int total = gridDim.x;
-  int logical = blockIdx.x;
-  if ((total & 7) == 0) logical = (blockIdx.x & 7) * (total >> 3) + (blockIdx.x >> 3);
-  // (32-bit unsigned index arithmetic in the prologue -- the host refuses positions * channels >= 2^30; see conv_bn.hip)
+  const int logical = xcd_logical();
+  // (32-bit unsigned index arithmetic in the prologue -- the host refuses positions * channels >= 2^30; see conv_mfma.h)
   const int mtile = (int)((unsigned)logical / (unsigned)NT);
   const long m0 = (long)mtile * BT;
   const int n0 = (logical - mtile * NT) * BT;
@@ -105,16 +80,7 @@ void conv3x3_igemm_kernel(ConvArgs a) {
 #pragma unroll
   for (int p = 0; p < PASSES; p++) {
     const int row = p * RPP + lrow;
-    const long lm = m0 + row;
-    m_ok[p] = lm < M;
-    img[p] = py[p] = px[p] = 0;
-    if (m_ok[p]) {
-      const unsigned hw = (unsigned)(a.H * a.W), ulm = (unsigned)lm;
-      const unsigned im = ulm / hw, rem = ulm - im * hw, yy = rem / (unsigned)a.W;
-      img[p] = (int)im;
-      py[p] = (int)yy;
-      px[p] = (int)(rem - yy * (unsigned)a.W);
-    }
+    row_pixel(m0 + row, M, a.H, a.W, 1, m_ok[p], img[p], py[p], px[p]);
     wv[p] = n0 + row < a.Cout ? ((unsigned)((n0 + row) * 9 * a.Cin + lchunk * 4)) * 4u : kOob;
     st_off[p] = swz_bytes<BK>(row, lchunk);
   }
@@ -165,7 +131,6 @@ void conv3x3_igemm_kernel(ConvArgs a) {
     }
   };
 
-  static_assert(DEPTH == 1 || (DEPTH == 2 && !DEFORM), "two register sets: plain taps only");
   v4f ra[DEPTH][PASSES], rb[DEPTH][PASSES];
   auto load_set = [&](auto setc, int tap, int c) {     // c: first channel of the K step
     constexpr int S = decltype(setc)::value;
@@ -191,7 +156,7 @@ void conv3x3_igemm_kernel(ConvArgs a) {
       *reinterpret_cast<v4f*>(s_raw + buf * 2 * TILE + TILE + st_off[p]) = rb[S][p];
     }
   };
-  using Set0 = std::integral_constant<int, 0>;
+  // (the one-set forms conv_mfma_loop.inc calls at DEPTH = 1)
   auto load_step = [&](int tap, int c) { load_set(Set0{}, tap, c); };
   auto store_step = [&](int buf) { store_set(Set0{}, buf); };
 
@@ -224,101 +189,24 @@ void conv3x3_igemm_kernel(ConvArgs a) {
       set_tap(tap);
     }
   };
-  auto mfma_step = [&](int buf) {
-    const char* sb = s_raw + buf * 2 * TILE;
-#pragma unroll
-    for (int qq = 0; qq < QN; qq++) {
-      v4f fa[T], fb[T];
-#pragma unroll
-      for (int i = 0; i < T; i++) {       // tile i: 32 rows further = the same swizzle (f repeats every 16 / 32 rows)
-        fa[i] = *reinterpret_cast<const v4f*>(sb + fa_off[qq] + i * 32 * BK * 4);
-        fb[i] = *reinterpret_cast<const v4f*>(sb + fb_off[qq] + i * 32 * BK * 4);
-      }
-#pragma unroll
-      for (int kk = 0; kk < 4; kk++)
-#pragma unroll
-        for (int i = 0; i < T; i++)
-#pragma unroll
-          for (int j = 0; j < T; j++)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i][kk], fb[j][kk], acc[i][j], 0, 0, 0);
-    }
-  };
-  if constexpr (DEPTH == 1) {
-    load_step(tap, c);
-    store_step(0);
-    __syncthreads();
-    for (int step = 0; step < nsteps; step++) {
-      const int buf = step & 1;
-      const bool more = step + 1 < nsteps;
-      if (more) {
-        advance();
-        load_step(tap, c);            // in flight during the MFMAs below
-      }
-      mfma_step(buf);
-      if (more) store_step(buf ^ 1);   // the other buffer: its last readers passed the barrier of the previous step
-      __syncthreads();
-    }
-  } else {
-    // At the top of turn s: LDS buffer (s & 1) holds step s, register set (s + 1) & 1 holds step s + 1 (in flight), set
-    // (s & 1) is free and takes step s + 2; steady-state turns request unconditionally (counted waits: conv_bn.hip).
-    using Set1 = std::integral_constant<int, DEPTH - 1>;
-    load_set(Set0{}, tap, c);
-    if (nsteps > 1) {
-      advance();
-      load_set(Set1{}, tap, c);
-    }
-    store_set(Set0{}, 0);
-    __syncthreads();
-    int step = 0;
-    for (; step + 3 < nsteps; step += 2) {
-      advance();
-      load_set(Set0{}, tap, c);
-      mfma_step(0);
-      store_set(Set1{}, 1);
-      __syncthreads();
-      advance();
-      load_set(Set1{}, tap, c);
-      mfma_step(1);
-      store_set(Set0{}, 0);
-      __syncthreads();
-    }
-    while (step < nsteps) {
-      if (step + 2 < nsteps) {
-        advance();
-        load_set(Set0{}, tap, c);
-      }
-      mfma_step(0);
-      if (step + 1 < nsteps) store_set(Set1{}, 1);
-      __syncthreads();
-      if (++step >= nsteps) break;
-      if (step + 2 < nsteps) {
-        advance();
-        load_set(Set1{}, tap, c);
-      }
-      mfma_step(1);
-      if (step + 1 < nsteps) store_set(Set0{}, 0);
-      __syncthreads();
-      ++step;
-    }
-  }
-
+  auto mfma_step = [&](int buf) { ::mfma_step<BT, BK, KG>(s_raw, buf, fa_off, fb_off, acc); };
+#include "conv_mfma_loop.inc"
   // ---- KG = 2: the second group hands its partial tile over through LDS (the operand buffers are free now) ----
   if (KG == 2) {
     float* red = reinterpret_cast<float*>(s_raw);           // [wave & 3][T*T*16][64 lanes]
-    static_assert(KG == 1 || 4 * T * T * 16 * 64 * 4 <= 4 * TILE, "reduction buffer");
     if (kg == 1) {
 #pragma unroll
       for (int i = 0; i < T; i++)
 #pragma unroll
         for (int j = 0; j < T; j++)
 #pragma unroll
-          for (int e = 0; e < 16; e++) red[(((wave & 3) * T * T + i * T + j) * 16 + e) * 64 + lane] = acc[i][j][e];
+          for (int e = 0; e < 16; e++) red[red_index<T>(wave, lane, i, j, e)] = acc[i][j][e];
     }
     __syncthreads();
     if (kg == 1) return;
   }
 
-  // ---- epilogue: C/D layout of the 32x32 MFMA: column = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5)
+  // ---- epilogue: C/D layout of the 32x32 MFMA: column = lane & 31, row = cd_row(reg) + 4 * (lane >> 5)
   // A tile inside the map (round 6, conv_bn.hip's finding): raw buffer loads / stores with one 32-bit lane offset and the 16
   // row offsets in SGPRs instead of 16 predicated accesses with 64-bit addresses per 32 x 32 tile; same values, same order.
   // (the 64 x 64 tile only: on the 128 x 128 tile the extra live values cost the 127-VGPR kernel two spills, and its
@@ -336,7 +224,7 @@ void conv3x3_igemm_kernel(ConvArgs a) {
 #pragma unroll
       for (int e = 0; e < 16; e++)
         mk[e] = (a.rowmask && !a.partial)
-                    ? __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rm, mrow * 4u, (unsigned)(((e & 3) + 8 * (e >> 2)) * 4), 0))
+                    ? __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rm, mrow * 4u, (unsigned)(cd_row(e) * 4), 0))
                     : 1.f;
 #pragma unroll
       for (int j = 0; j < T; j++) {
@@ -348,14 +236,14 @@ void conv3x3_igemm_kernel(ConvArgs a) {
           for (int e = 0; e < 16; e++) {
             float v = acc[i][j][e];
             if (KG == 2)
-              v += reinterpret_cast<const float*>(s_raw)[(((wave & 3) * T * T + i * T + j) * 16 + e) * 64 + lane];
+              v += reinterpret_cast<const float*>(s_raw)[red_index<T>(wave, lane, i, j, e)];
             if (!a.partial) {
               v += b;
               if (a.relu) v = fmaxf(v, 0.f);
               if (a.rowmask) v *= mk[e];
             }
             __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), ry, base,
-                                                  (unsigned)(((e & 3) + 8 * (e >> 2)) * a.Cout * 4), 0);
+                                                  (unsigned)(cd_row(e) * a.Cout * 4), 0);
           }
         }
       }
@@ -380,7 +268,7 @@ void conv3x3_igemm_kernel(ConvArgs a) {
         if (m < M && n < a.Cout) {
           float v = acc[i][j][e];
           if (KG == 2)      // the other wave group's partial sum (read tile by tile: no second accumulator set live)
-            v += reinterpret_cast<const float*>(s_raw)[(((wave & 3) * T * T + i * T + j) * 16 + e) * 64 + lane];
+            v += reinterpret_cast<const float*>(s_raw)[red_index<T>(wave, lane, i, j, e)];
           if (a.partial) {
             a.partial[((size_t)blockIdx.y * M + m) * a.Cout + n] = v;
           } else {
@@ -424,13 +312,6 @@ int launch(const ConvArgs& a, hipStream_t st) {
     hipLaunchKernelGGL((conv3x3_igemm_kernel<BT, BK, KG, true>), dim3((unsigned)tiles, a.ksplit), dim3(256 * KG), 0, st, a);
     return jdet_launch_status();
   }
-  if constexpr (BT == 64 && KG == 1) {
-    static const char* e = getenv("JDET_CONV_IGEMM_DEEP");      // operand tiles two K steps ahead (A/B switch; default on)
-    if (!e || atoi(e) != 0) {
-      hipLaunchKernelGGL((conv3x3_igemm_kernel<BT, BK, KG, false, 2>), dim3((unsigned)tiles, a.ksplit), dim3(256), 0, st, a);
-      return jdet_launch_status();
-    }
-  }
   hipLaunchKernelGGL((conv3x3_igemm_kernel<BT, BK, KG, false>), dim3((unsigned)tiles, a.ksplit), dim3(256 * KG), 0, st, a);
   return jdet_launch_status();
 }
@@ -443,13 +324,8 @@ JDET_API int jdet_conv3x3_igemm_supported(int Cin, int Cout) { return Cin > 0 &&
 // Cross-workgroup K split for small maps (a tile's 2304-deep reduction is otherwise the floor of the launch): how many
 // ways a problem is split when a workspace is offered, and the bytes that takes.  1 = no split.
 static int ksplit_for(long M, int Cin, int Cout, bool deform) {
-  const long tiles64 = ((M + 63) / 64) * ((Cout + 63) / 64);
-  if (deform || Cout % 4 != 0 || tiles64 >= 384) return 1;
-  const int steps = 9 * (Cin / (Cin % 32 == 0 ? 32 : 16));
-  int k = (int)(768 / tiles64);                 // aim at ~3 workgroups per CU
-  if (k > 8) k = 8;
-  if (k > steps / 4) k = steps / 4;             // at least 4 K steps per part
-  return k < 2 ? 1 : k;
+  if (deform || Cout % 4 != 0) return 1;
+  return ksplit_rule(((M + 63) / 64) * ((Cout + 63) / 64), 9 * (Cin / (Cin % 32 == 0 ? 32 : 16)));
 }
 
 JDET_API size_t jdet_conv3x3_igemm_workspace(int N, int H, int W, int Cin, int Cout) {

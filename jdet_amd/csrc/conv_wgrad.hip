@@ -29,14 +29,9 @@
 //     x, x + 8, ... and runs ALL (Cout tile, Cin tile, tap) workgroups of a chunk back to back: the 9 taps x Cout tiles
 //     that re-read the same positions of X (and the 9 taps x Cin tiles re-reading gY) find them in that XCD's L2.
 // The matrix pipe is the bound: 2 * 9 * Cin * Cout * positions flop at 157 TFLOP/s.
-#include <cstdlib>
-
-#include "common.h"
+#include "conv_mfma.h"      // v4f / v16f, kOob, buf_load, out_dim: the tiling and the loop here are this file's own
 
 namespace {
-
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef float v16f __attribute__((ext_vector_type(16)));
 
 struct WgradArgs {
   const float* x;        // (N, H, W, Cin)
@@ -47,12 +42,7 @@ struct WgradArgs {
   int R, stride, Ho, Wo;   // R x R taps (pad R / 2), stride: gy is (N, Ho, Wo, Cout); 3 / 1 / H / W for the 3x3 form
 };
 
-constexpr unsigned kOob = 0xFFFFFFF0u;
 constexpr int BK = 16;
-
-__device__ __forceinline__ v4f buf_load(__amdgpu_buffer_rsrc_t r, unsigned voff) {
-  return __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(r, voff, 0, 0));
-}
 
 // S2: the strided form (stride 2, or any case where the x pixel of a position is not at a constant distance from it)
 template <int TM, int TN, bool DEFORM, bool WIDE, bool S2, int DEPTH = 1>
@@ -185,13 +175,13 @@ void conv3x3_wgrad_kernel(WgradArgs a) {
     constexpr int S = decltype(setc)::value;
 #pragma unroll
     for (int p = 0; p < PA; p++) {
-      ra[S][p] = buf_load(rg, a_off[p]);          // past the last position: out of range -> 0
+      ra[S][p] = buf_load(rg, a_off[p], 0);          // past the last position: out of range -> 0
       a_off[p] += a_step;
     }
 #pragma unroll
     for (int p = 0; p < PB; p++) {
       if constexpr (!DEFORM) {
-        rb[S][p][0] = buf_load(rx, b_off[p][0]);
+        rb[S][p][0] = buf_load(rx, b_off[p][0], 0);
       } else {
         // dcn_v1.py:L132-166 (deformable_im2col), the same sampling rule as conv_igemm.hip's gathered operand
         const bool ok = b_cok && bp[p] < M;
@@ -206,7 +196,7 @@ void conv3x3_wgrad_kernel(WgradArgs a) {
           const bool kin = in && (unsigned)cy[k] < (unsigned)a.H && (unsigned)cx[k] < (unsigned)a.W;
           wt[p][k] = w4[k];
           rb[S][p][k] = buf_load(rx, kin ? ((unsigned)(((bi[p] * a.H + cy[k]) * a.W + cx[k]) * a.Cin + n0 + b_chunk * 4)) * 4u
-                                         : kOob);
+                                         : kOob, 0);
         }
         advance(p);
         fetch_offsets(p);
@@ -368,35 +358,25 @@ int launch(const WgradArgs& a, hipStream_t st) {
   const unsigned grid = (unsigned)(mt * nt * a.R * a.R * ((a.ksplit + 7) & ~7));
   const bool wide = a.Wo >= BK;
   const bool s2 = a.stride != 1 || a.Ho != a.H || a.Wo != a.W;
-  static const char* deep_env = getenv("JDET_CONV_WGRAD_DEEP");      // rows 4 (wide stride-1 form) / 2 K steps ahead; 0 / 2 / 4: A/B
-  // the 64 x 64 tile only: the wider tiles' K step is long enough for one step of cover, and several register sets on top
-  // of their accumulators spill (<2, 2, ..., 4>: 124 VGPRs to scratch -- the head towers' gradients through this kernel
-  // ran 3.4 ms per step slower with it)
-  static const char* mid_env = getenv("JDET_CONV_WGRAD_DEEP_MID");   // the 128 x 64 / 64 x 128 tiles: 0 (default) / 2
-  const int deep_n = (TM == 1 && TN == 1) ? (deep_env ? atoi(deep_env) : 4)
-                                          : ((TM + TN == 3 && mid_env) ? (atoi(mid_env) ? 2 : 0) : 0);
-  const bool deep = deep_n != 0, deep4 = deep_n == 4;
+  // Register sets of the plain form (K steps its rows are requested ahead): four for the 64 x 64 wide stride-1 form, two for
+  // its narrow and strided forms, one for every wider tile -- their K step is long enough for one step of cover, and
+  // several register sets on top of their accumulators spill (<2, 2, ..., 4>: 124 VGPRs to scratch -- the head towers'
+  // gradients through this kernel ran 3.4 ms per step slower with it; two sets on the 128 x 64 / 64 x 128 tiles measured
+  // no gain, profiles/r06_conv_prefetch.md) -- and for the deformable form (see the kernel).
+  constexpr bool SMALL = TM == 1 && TN == 1;
+  constexpr int D2 = SMALL ? 2 : 1, D4 = SMALL ? 4 : 1;
   if (a.offset) {
     if (wide) hipLaunchKernelGGL((conv3x3_wgrad_kernel<TM, TN, true, true, false>), dim3(grid), dim3(256), 0, st, a);
     else hipLaunchKernelGGL((conv3x3_wgrad_kernel<TM, TN, true, false, false>), dim3(grid), dim3(256), 0, st, a);
   } else if (s2) {
-    constexpr int D2 = (TM + TN <= 3) ? 2 : 1;
-    if (wide && deep) hipLaunchKernelGGL((conv3x3_wgrad_kernel<TM, TN, false, true, true, D2>), dim3(grid), dim3(256), 0, st, a);
-    else if (wide) hipLaunchKernelGGL((conv3x3_wgrad_kernel<TM, TN, false, true, true>), dim3(grid), dim3(256), 0, st, a);
-    else if (deep) hipLaunchKernelGGL((conv3x3_wgrad_kernel<TM, TN, false, false, true, D2>), dim3(grid), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((conv3x3_wgrad_kernel<TM, TN, false, false, true>), dim3(grid), dim3(256), 0, st, a);
+    if (wide) hipLaunchKernelGGL((conv3x3_wgrad_kernel<TM, TN, false, true, true, D2>), dim3(grid), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((conv3x3_wgrad_kernel<TM, TN, false, false, true, D2>), dim3(grid), dim3(256), 0, st, a);
   } else {
-    constexpr int D2 = (TM + TN <= 3) ? 2 : 1, D4 = (TM == 1 && TN == 1) ? 4 : 1;
-    if (wide && deep4) hipLaunchKernelGGL((conv3x3_wgrad_kernel<TM, TN, false, true, false, D4>), dim3(grid), dim3(256), 0, st, a);
-    else if (wide && deep) hipLaunchKernelGGL((conv3x3_wgrad_kernel<TM, TN, false, true, false, D2>), dim3(grid), dim3(256), 0, st, a);
-    else if (wide) hipLaunchKernelGGL((conv3x3_wgrad_kernel<TM, TN, false, true, false>), dim3(grid), dim3(256), 0, st, a);
-    else if (deep) hipLaunchKernelGGL((conv3x3_wgrad_kernel<TM, TN, false, false, false, D2>), dim3(grid), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((conv3x3_wgrad_kernel<TM, TN, false, false, false>), dim3(grid), dim3(256), 0, st, a);
+    if (wide) hipLaunchKernelGGL((conv3x3_wgrad_kernel<TM, TN, false, true, false, D4>), dim3(grid), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((conv3x3_wgrad_kernel<TM, TN, false, false, false, D2>), dim3(grid), dim3(256), 0, st, a);
   }
   return jdet_launch_status();
 }
-
-int wgrad_out_dim(int in, int R, int stride) { return (in + 2 * (R / 2) - R) / stride + 1; }
 
 // general = the backbone's entry point (jdet_conv_wgrad): 64 x 64 tiles and a split aimed at ~2300 workgroups of at
 // least 32 K steps -- measured at every ResNet-50 layer shape of a 2 x 1024^2 step (scripts/conv_bn_timing.py wgrad,
@@ -405,7 +385,7 @@ int wgrad_out_dim(int in, int R, int stride) { return (in + 2 * (R / 2) - R) / s
 // 128 -> 128: 90 vs 104 us).
 int run_wgrad(const float* x_nhwc, const float* gy_nhwc, const float* offset, int N, int H, int W, int Cin, int Cout,
               int R, int stride, float* gw, int ksplit, hipStream_t st, bool general = false) {
-  const int Ho = wgrad_out_dim(H, R, stride), Wo = wgrad_out_dim(W, R, stride);
+  const int Ho = out_dim(H, R, stride), Wo = out_dim(W, R, stride);
   const long M = (long)N * Ho * Wo, Mx = (long)N * H * W;
   if ((M + BK) * Cout >= (1L << 30) || (Mx + BK) * Cin >= (1L << 30)) return JDET_E_UNSUPPORTED;     // 32-bit byte offsets
   // bit 17: 64 x 64 tiles whatever the channel counts, bit 18: 128-wide tiles where the channels allow (measurement aids)
@@ -413,7 +393,7 @@ int run_wgrad(const float* x_nhwc, const float* gy_nhwc, const float* offset, in
   int tm = (Cout > 64 && !small) ? 2 : 1, tn = (Cin > 64 && !small) ? 2 : 1;
   // Round 6: 128 x 64 instead of 128 x 128 for the plain form -- the head towers' shape (2 x 128^2, 256 -> 256): 310 us
   // against 360 (128 x 128: 128 VGPRs, three of them spilled), 332 (64 x 64) and the library's 326 incl. its zero fill
-  // (scripts/wgrad_tiles_p3.sh, profiles/r06_conv_prefetch.md).  Bit 21 keeps the 128 x 128 tile (A/B).
+  // (profiles/r06_conv_prefetch.md).  Bit 21 keeps the 128 x 128 tile (A/B).
   if (tm == 2 && tn == 2 && !offset && !((ksplit >> 21) & 1)) tn = 1;
   if ((ksplit >> 19) & 1) tn = 1;        // bit 19: 128 x 64 tiles, bit 20: 64 x 128 (measurement aids)
   if ((ksplit >> 20) & 1) tm = 1;

@@ -73,6 +73,12 @@ def _bn_params(bn):
     return L.BnParams(L.ptr(bn.weight), L.ptr(bn.bias), L.ptr(bn.running_mean), L.ptr(bn.running_var), float(bn.eps))
 
 
+def epilogue(mode=L.EPI_FORWARD, bn=None, relu=False, residual=None, grad_out=None, act=None, sums=None):
+    """the jdet_conv_epilogue_t of one launch (the tensors must outlive it)"""
+    return L.ConvEpilogue(mode, 1 if (bn is not None and mode == L.EPI_FORWARD) else 0, 1 if relu else 0, _bn_params(bn),
+                          L.ptr(residual), L.ptr(grad_out), L.ptr(act), L.ptr(sums))
+
+
 def _plan(N, H, W, Cin, Cout, R, stride):
     key = (N, H, W, Cin, Cout, R, stride)
     hit = _PLAN.get(key)
@@ -117,8 +123,7 @@ def conv_bn_nhwc(x, w_krsc, stride=1, bn=None, residual=None, relu=False, mode=L
         if tile != 0:
             rows = lib.jdet_conv_bn_sums_rows(N, H, W, Cin, Cout, R, stride, tile, 0)
         sums = torch.empty((rows, 2, Cout), dtype=torch.float32, device=x.device)
-    ep = L.ConvEpilogue(mode, 1 if (bn is not None and mode == L.EPI_FORWARD) else 0, 1 if relu else 0, _bn_params(bn),
-                        L.ptr(residual), L.ptr(grad_out), L.ptr(act), L.ptr(sums))
+    ep = epilogue(mode, bn, relu, residual, grad_out, act, sums)
     L.check(lib.jdet_conv_bn_forward(L.ptr(x), N, H, W, Cin, L.ptr(w_krsc), Cout, R, stride, ctypes.byref(ep), int(tile),
                                      L.ptr(y), L.ptr(ws), ws_bytes, L.stream_ptr(x)), "jdet_conv_bn_forward")
     return (y, sums) if mode == L.EPI_MASK else y

@@ -1,13 +1,15 @@
 #!/usr/bin/env python3
 """Round 6: where the time of a conv_bn 64 x 64-tile launch goes ACROSS the chip -- workgroup time stamps.
 
-JDET_CONV_BN_ABL=16 launches conv_bn_kernel<64, 32, 1, 2, 16>: every workgroup writes wall_clock64() at its start, when it
-enters / leaves the K loop and at its end, plus HW_ID / XCC_ID / blockIdx, over the first 12 words of its tile's first
-output row (a profiling build: those words are garbage afterwards).  Per layer: kernel span, workgroup lifetimes, the split
-prologue | K loop | epilogue, workgroups per CU (placement), and what the K loop alone would take at 64 cycles per MFMA.
+jdet_conv_bn_forward_stamps (libjdet_experimental.so, csrc/experimental/conv_bn_stamps.hip) launches the profiling build
+conv_bn_kernel<64, 32, 1, 2, true>: every workgroup writes wall_clock64() at its start, when it enters / leaves the K loop
+and at its end, plus HW_ID / XCC_ID / blockIdx, over the first 16 words of its tile's first output row (those words are
+garbage afterwards).  Per layer: kernel span, workgroup lifetimes, the split prologue | K loop | epilogue, workgroups per CU
+(placement), and what the K loop alone would take at 64 cycles per MFMA.
 
-    JDET_CONV_BN_ABL=16 python scripts/r6_conv_stamps.py
+    python scripts/r6_conv_stamps.py
 """
+import ctypes
 import os
 import sys
 
@@ -15,7 +17,8 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-os.environ.setdefault("JDET_CONV_BN_ABL", "16")
+from jdet_amd import _experimental as X  # noqa: E402
+from jdet_amd import _lib as L  # noqa: E402
 from jdet_amd.ops import conv_bn as CB  # noqa: E402
 
 dev = torch.device("cuda:0")
@@ -25,20 +28,31 @@ LAYERS = [("l1.conv2", 2, 256, 256, 64, 64, 3), ("l2.conv2", 2, 128, 128, 128, 1
 TICK = 1e-2          # wall_clock64: 100 MHz -> 0.01 us
 
 
+def conv_bn_stamps(x, w_krsc, stride, bn, relu):
+    """conv_bn_nhwc's forward mode through the stamps build: (N, Ho, Wo, Cout) with the stamp words in it"""
+    N, H, W, Cin = x.shape
+    Cout, R = w_krsc.shape[0], w_krsc.shape[1]
+    y = torch.empty((N, CB.out_size(H, R, stride), CB.out_size(W, R, stride), Cout), dtype=torch.float32, device=x.device)
+    ep = CB.epilogue(L.EPI_FORWARD, bn, relu)
+    L.check(X.lib().jdet_conv_bn_forward_stamps(L.ptr(x), N, H, W, Cin, L.ptr(w_krsc), Cout, R, stride, ctypes.byref(ep),
+                                                L.ptr(y), L.stream_ptr(x)), "jdet_conv_bn_forward_stamps")
+    return y
+
+
 def main():
     for name, N, H, W, Ci, Co, R in LAYERS:
         x = torch.randn(N, H, W, Ci, device=dev)
         w = torch.randn(Co, R, R, Ci, device=dev) / (R * Ci ** 0.5)
         bn = torch.nn.BatchNorm2d(Co).to(dev).eval()
         for _ in range(10):
-            y = CB.conv_bn_nhwc(x, w, 1, bn, None, True)
+            y = conv_bn_stamps(x, w, 1, bn, True)
         torch.cuda.synchronize()
         M = N * H * W
         rows = y.reshape(M, Co)[::64]                                   # first row of every M tile
         words = rows.reshape(rows.shape[0], Co // 64, 64)[:, :, :16].contiguous().view(torch.int32).cpu().numpy().astype(np.int64)
         words = words.reshape(-1, 16)
         ok = (words[:, 11] == 0x5741)
-        assert ok.all(), "%s: %d of %d tiles without stamps (is JDET_CONV_BN_ABL=16 set?)" % (name, (~ok).sum(), len(ok))
+        assert ok.all(), "%s: %d of %d tiles without stamps" % (name, (~ok).sum(), len(ok))
         t = [(words[:, 2 * k] & 0xffffffff) | (words[:, 2 * k + 1] << 32) for k in range(4)]
         base = t[0].min()
         s, l0, l1, e = [(v - base) * TICK for v in t]
