@@ -272,7 +272,7 @@ int jdet_conv3x3_igemm_forward(const float* x_nhwc, int N, int H, int W, int Cin
                                jdet_stream_t stream);
 /* optional workspace: maps too small to fill the chip with output tiles are split along K over workgroups (partial
  * tiles summed by a second launch that also applies the epilogue) when a workspace of this size is passed; NULL / 0 =
- * single pass.  0 when the shape is not split. */
+ * single pass.  0 when the shape is not split.  A non-NULL workspace of fewer bytes than the query: JDET_E_WORKSPACE. */
 size_t jdet_conv3x3_igemm_workspace(int N, int H, int W, int Cin, int Cout);
 
 /* Weight gradient of the same convolution, ACCUMULATED into gw: gw (Cout,3,3,Cin) += sum over positions of
@@ -327,8 +327,9 @@ typedef struct jdet_conv_epilogue {
 /* x (N,H,W,Cin), w (Cout,R,R,Cin), y (N,Ho,Wo,Cout), Ho = (H + 2*(R/2) - R) / stride + 1; R in {1, 3}, stride in
  * {1, 2}, Cin % 16 == 0, 16-byte aligned x / w, positions * channels < 2^30 (else JDET_E_UNSUPPORTED / _BADARG).
  * tile: as jdet_conv3x3_igemm_forward.  workspace (jdet_conv_bn_workspace bytes, optional): small maps split their K
- * steps over workgroups.  jdet_conv_bn_sums_rows: rows of `sums` a MASK launch with these arguments writes
- * (with_workspace: whether a sufficient workspace will be passed). */
+ * steps over workgroups; NULL / 0 bytes = single pass, a non-NULL workspace of fewer bytes than the query with tile 0:
+ * JDET_E_WORKSPACE (the single pass writes more rows of `sums`).  jdet_conv_bn_sums_rows: rows of `sums` a MASK launch
+ * with these arguments writes (with_workspace: whether a sufficient workspace will be passed). */
 int jdet_conv_bn_supported(int Cin, int Cout, int R, int stride);
 size_t jdet_conv_bn_workspace(int N, int H, int W, int Cin, int Cout, int R, int stride);
 size_t jdet_conv_bn_sums_rows(int N, int H, int W, int Cin, int Cout, int R, int stride, int tile,

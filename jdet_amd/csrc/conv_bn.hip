@@ -219,6 +219,9 @@ JDET_API int jdet_conv_bn_forward(const float* x_nhwc, int N, int H, int W, int 
   const int edge = tile & ~3;
   if (tile != 0 && edge != 64 && edge != 128) return JDET_E_BADARG;
   const size_t need_ws = jdet_conv_bn_workspace(N, H, W, Cin, Cout, R, stride);
+  // a workspace that is offered but too small is refused, not ignored: without the K split a MASK launch writes twice
+  // the partial-sum rows, past the end of a `sums` the caller sized with jdet_conv_bn_sums_rows(..., with_workspace = 1)
+  if (tile == 0 && workspace && workspace_bytes && workspace_bytes < need_ws) return JDET_E_WORKSPACE;
   bool ws_ok = workspace && need_ws && workspace_bytes >= need_ws;
   // the finish kernel moves float4s
   if (ws_ok && ((((uintptr_t)y_nhwc) | ((uintptr_t)workspace) | ((uintptr_t)ep.residual) | ((uintptr_t)ep.grad_out) |

@@ -362,6 +362,9 @@ JDET_API int jdet_conv3x3_igemm_forward(const float* x_nhwc, int N, int H, int W
   hipStream_t st = (hipStream_t)stream;
   if (tile == 0 && !big) {
     const int ks = ksplit_for(M, Cin, Cout, offset != nullptr);
+    // offered but too small: refused like every other workspace (NULL / 0 bytes = single pass)
+    if (ks > 1 && workspace && workspace_bytes && workspace_bytes < sizeof(float) * (size_t)ks * M * Cout)
+      return JDET_E_WORKSPACE;
     if (ks > 1 && workspace && workspace_bytes >= sizeof(float) * (size_t)ks * M * Cout) {
       // the finish kernel moves float4s: y, bias and the scratch must be 16-byte aligned as well (views at odd offsets)
       if ((((uintptr_t)y_nhwc) | ((uintptr_t)bias) | ((uintptr_t)workspace)) & 15 || Cout % 4 != 0) goto unsplit;
