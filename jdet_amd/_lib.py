@@ -148,6 +148,13 @@ SIGNATURES = {
     "jdet_assign_max_iou": (_i, [_p, _i, _i, _f, _f, _f, _f, _i, _i, _p, _i, _p, _p, _p, _p, _sz, _p]),
 }
 
+# include/jdet_hip_atss.h (same library; a table of its own until the contract table of tests/abi_cases.py is next
+# revised -- the header says why; tests/test_atss_cpu.py checks it against the header and the exports)
+ATSS_SIGNATURES = {
+    "jdet_atss_assign_workspace": (_sz, [_i, _i, _i, _i]),
+    "jdet_atss_assign": (_i, [_p, _i, _i, _p, _i, _p, _i, _p, _p, _i, _i, _p, _p, _p, _p, _sz, _p]),
+}
+
 _lib = None
 
 # Hull-point ordering inside the rotated IoU: 0 = the reference's CPU path (std::sort,
@@ -178,7 +185,7 @@ def lib():
         # process and our DT_NEEDED entry resolves to that same runtime: one HIP context, shared
         # streams and allocations.
         l = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(ATSS_SIGNATURES.items()):
             fn = getattr(l, name)  # AttributeError here == ABI drift: fail loudly
             fn.restype = res
             fn.argtypes = args

@@ -150,6 +150,32 @@ KFIOU_RETINANET_CFG = _gaussian_retinanet_cfg(
     "KFIoURRetinaHead", dict(type="KFLoss", loss_weight=5.0), False)
 
 
+ATSS_RETINANET_CFG = dict(
+    # configs/rotated_retinanet/rotated_retinanet_obb_r50_fpn_1x_dota_atss.py: model L2-55, optimizer L128-135,
+    # scheduler L137-142 (tests/golden/configs/rotated_retinanet_obb_r50_fpn_1x_dota_atss.yaml holds them as `Config`
+    # reads them).  One square anchor per location; ATSS picks 9 candidates per level and gt.
+    model=dict(
+        type="RotatedRetinaNet",
+        backbone=dict(type="Resnet50", frozen_stages=1, return_stages=["layer1", "layer2", "layer3", "layer4"],
+                      pretrained=True),
+        neck=dict(type="FPN", in_channels=[256, 512, 1024, 2048], out_channels=256, start_level=1,
+                  add_extra_convs="on_input", num_outs=5),
+        bbox_head=dict(
+            type="RotatedATSSHead", num_classes=16, in_channels=256, feat_channels=256, stacked_convs=4,
+            octave_base_scale=4, scales_per_octave=1, anchor_ratios=[1.0], anchor_strides=[8, 16, 32, 64, 128],
+            target_means=[.0, .0, .0, .0, .0], target_stds=[1.0, 1.0, 1.0, 1.0, 1.0],
+            loss_cls=dict(type="FocalLoss", use_sigmoid=True, gamma=2.0, alpha=0.25, loss_weight=1.0),
+            loss_bbox=dict(type="L1Loss", loss_weight=1.0),
+            test_cfg=dict(nms_pre=2000, min_bbox_size=0, score_thr=0.05, nms=dict(type="nms_rotated", iou_thr=0.1),
+                          max_per_img=2000),
+            train_cfg=dict(
+                assigner=dict(type="ATSSAssignerRbbox", topk=9, iou_calculator=dict(type="BboxOverlaps2D_rotated")),
+                bbox_coder=dict(type="DeltaXYWHABBoxCoder", target_means=(0., 0., 0., 0., 0.),
+                                target_stds=(1., 1., 1., 1., 1.), clip_border=True),
+                allowed_border=-1, pos_weight=-1, debug=False))),
+    **_SGD_1X)
+
+
 GLIDING_CFG = dict(
     # configs/gliding_r50_fpn_1x_dota_with_flip.py: model L2-116, optimizer L195, scheduler L197-202
     # (tests/golden/configs/gliding_r50_fpn_1x_dota_with_flip.yaml holds them as `Config` reads them)

@@ -120,9 +120,20 @@ def anchor_target_dense(anchor_list, gt_bboxes_list, gt_labels_list, cfg):
     """Fixed-shape twin of `anchor_target` (same values): per image one IoU launch, the fused assigner and
     ONE fused target launch (jdet_anchor_targets_rotated) instead of nonzero + 6 index scatters; the number of
     positives stays on the device.  anchor_list: per image a (A,5) tensor."""
-    from jdet_amd import _lib as L
     assigner = build_from_cfg(cfg.get("assigner", ""), BOXES)
-    coder = build_from_cfg(cfg.get("bbox_coder", ""), BOXES)
+    return dense_targets(anchor_list, gt_bboxes_list, gt_labels_list, cfg,
+                         lambda anchors, gt: assigner.assign(anchors, gt, None, None).gt_inds)
+
+
+def dense_targets(anchor_list, gt_bboxes_list, gt_labels_list, cfg, assign_fn):
+    """The part of the dense route every assigner shares: per image `assign_fn(anchors, gt)` -> gt_inds (A) int32
+    (0 negative, -1 ignored, i + 1 = gt i), then ONE fused target launch.  Returns (labels (n, A), label_weights
+    (n, A), bbox_targets (n, A, 5), bbox_weights (n, A, 5), sum_img max(npos_img, 1) as a 0-dim device tensor)."""
+    from jdet_amd import _lib as L
+    decoded = cfg.get("reg_decoded_bbox", False)
+    if not decoded:
+        coder = build_from_cfg(cfg.get("bbox_coder", ""), BOXES)
+        means, stds = L.vec5(coder.means), L.vec5(coder.stds)
     pos_weight = cfg.get("pos_weight", -1)
     pos_weight = 1.0 if pos_weight <= 0 else float(pos_weight)
     num_imgs = len(anchor_list)
@@ -133,20 +144,18 @@ def anchor_target_dense(anchor_list, gt_bboxes_list, gt_labels_list, cfg):
     bbox_targets = torch.empty((num_imgs, A, 5), dtype=torch.float32, device=dev)
     bbox_weights = torch.empty((num_imgs, A, 5), dtype=torch.float32, device=dev)
     num_pos = torch.zeros((num_imgs,), dtype=torch.int32, device=dev)
-    means, stds = L.vec5(coder.means), L.vec5(coder.stds)
-    decoded = cfg.get("reg_decoded_bbox", False)
     for i in range(num_imgs):
         anchors, gt = L.f32c(anchor_list[i]), L.f32c(gt_bboxes_list[i])
-        res = assigner.assign(anchors, gt, None, None)
+        gt_inds = assign_fn(anchors, gt)
         gl = gt_labels_list[i].to(torch.int32).contiguous() if gt_labels_list[i] is not None else None
         if decoded:     # the assigned gt boxes themselves (anchor_target.py:L79-80), copied in the same launch
             L.check(L.lib().jdet_anchor_targets_rotated_boxes(
-                L.ptr(gt), L.ptr(gl), L.ptr(res.gt_inds), A, gt.shape[0], pos_weight, L.ptr(labels[i]),
+                L.ptr(gt), L.ptr(gl), L.ptr(gt_inds), A, gt.shape[0], pos_weight, L.ptr(labels[i]),
                 L.ptr(label_weights[i]), L.ptr(bbox_targets[i]), L.ptr(bbox_weights[i]), L.ptr(num_pos[i:i + 1]),
                 L.stream_ptr(anchors)), "jdet_anchor_targets_rotated_boxes")
             continue
         L.check(L.lib().jdet_anchor_targets_rotated(
-            L.ptr(anchors), L.ptr(gt), L.ptr(gl), L.ptr(res.gt_inds), A, gt.shape[0], means, stds, pos_weight,
+            L.ptr(anchors), L.ptr(gt), L.ptr(gl), L.ptr(gt_inds), A, gt.shape[0], means, stds, pos_weight,
             L.ptr(labels[i]), L.ptr(label_weights[i]), L.ptr(bbox_targets[i]), L.ptr(bbox_weights[i]),
             L.ptr(num_pos[i:i + 1]), L.stream_ptr(anchors)), "jdet_anchor_targets_rotated")
     # sum_img max(npos_img, 1) (anchor_target.py:L77) as a 0-dim device tensor: the loss normaliser never

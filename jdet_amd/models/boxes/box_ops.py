@@ -1,6 +1,6 @@
 """Rotated box algebra used by the named configs.  Mirrors python/jdet/models/boxes/box_ops.py:
 norm_angle L176-178, bbox2delta_rotated L180-226, delta2bbox_rotated L229-285,
-rotated_box_to_poly L592-613.
+rotated_box_to_poly L592-613, points_in_rotated_boxes L725-741.
 
 On a HIP device and outside autograd the two coders run as ONE fused kernel each
 (csrc/box_codec_assign.hip); the torch expressions below are the differentiable form (needed when
@@ -96,3 +96,17 @@ def rotated_box_to_poly(rrects):
     px = c * xs - s_ * ys + x_ctr[:, None]
     py = s_ * xs + c * ys + y_ctr[:, None]
     return torch.stack([px, py], dim=2).reshape(n, 8)
+
+
+def points_in_rotated_boxes(points, rrects):
+    """(n, 2+) points x (m, 5) boxes -> (n, m) bool, True where the point lies inside the box.  The tensor program of
+    box_ops.py:L725-741 as written (atan2 of the offset, cos / sin of the angle difference), kept for API parity: the
+    fused assigner (csrc/atss_assign.hip) tests only its candidates, in the algebraic form stated in
+    include/jdet_hip_atss.h."""
+    offsets = points[:, None, :2] - rrects[None, :, :2]
+    offset_angles = torch.atan2(offsets[..., 1], offsets[..., 0])
+    offset_distances = offsets.square().sum(-1).sqrt()
+    delta_angles = offset_angles - rrects[None, :, 4]
+    delta_w = torch.abs(offset_distances * torch.cos(delta_angles))
+    delta_h = torch.abs(offset_distances * torch.sin(delta_angles))
+    return (delta_w < rrects[None, :, 2] / 2) & (delta_h < rrects[None, :, 3] / 2)

@@ -3,6 +3,7 @@ from .oriented_rpn_head import OrientedRPNHead  # noqa: F401
 from .s2anet_head import AlignConv, S2ANetHead, bbox_decode  # noqa: F401
 from .rotated_retina_head import RotatedRetinaHead  # noqa: F401
 from .kfiou_rotated_retina_head import KFIoURRetinaHead  # noqa: F401
+from .rotated_atss_head import RotatedATSSHead  # noqa: F401
 from .rbbox_head import BBoxHeadRbbox  # noqa: F401
 from .convfc_rbbox_head import ConvFCBBoxHeadRbbox, SharedFCBBoxHeadRbbox  # noqa: F401
 from .fasterrcnn_head import AnchorHead, FasterrcnnHead  # noqa: F401

@@ -1,0 +1,176 @@
+"""RetinaNet-OBB head with ATSS assignment.  Mirrors python/jdet/models/roi_heads/rotated_atss_head.py:L19-250: a
+RotatedRetinaHead whose `anchor_target` / `anchor_target_single` hand the number of anchors per level to the assigner
+(ATSSAssignerRbbox picks its candidates level by level).
+
+Two routes, same values:
+  dense    every anchor valid, `allowed_border < 0`, no ignore boxes, PseudoSampler, DeltaXYWHABBoxCoder targets (or the
+           gt boxes themselves with `reg_decoded_bbox`), device tensors -- what every config hits.  Per image
+           jdet_atss_assign (three launches) and ONE fused target launch; the number of positives stays on the device
+           (models/boxes/anchor_target.py: dense_targets), so the step has no host sync and captures into a graph.
+  general  inside flags, the per-level count of inside anchors on the host (L236-250), index lists, `unmap`."""
+import torch
+
+from jdet_amd.models.boxes.anchor_target import anchor_inside_flags, dense_targets, images_to_levels
+from jdet_amd.models.boxes.sampler import PseudoSampler
+from jdet_amd.utils.general import multi_apply, unmap
+from jdet_amd.utils.registry import BOXES, HEADS, build_from_cfg
+
+from .rotated_retina_head import RotatedRetinaHead
+from .s2anet_head import _cfg
+
+_ATSS_ASSIGN = dict(
+    assigner=dict(type="ATSSAssignerRbbox", topk=9, iou_calculator=dict(type="BboxOverlaps2D_rotated")),
+    bbox_coder=dict(type="DeltaXYWHABBoxCoder", target_means=(0., 0., 0., 0., 0.), target_stds=(1., 1., 1., 1., 1.),
+                    clip_border=True),
+    allowed_border=-1, pos_weight=-1, debug=False)
+
+
+def get_num_level_anchors_inside(num_level_anchors, inside_flags):
+    """number of inside anchors of every level, as host integers (L236-250: one device -> host read per level)"""
+    return [int(flags.sum()) for flags in torch.split(inside_flags, num_level_anchors)]
+
+
+@HEADS.register_module()
+class RotatedATSSHead(RotatedRetinaHead):
+    def __init__(self, num_classes, in_channels, feat_channels=256, stacked_convs=4, octave_base_scale=4,
+                 scales_per_octave=1, anchor_ratios=[1.0], anchor_strides=[8, 16, 32, 64, 128],
+                 anchor_base_sizes=None, target_means=(.0, .0, .0, .0, .0), target_stds=(1.0, 1.0, 1.0, 1.0, 1.0),
+                 loss_cls=dict(type="FocalLoss", use_sigmoid=True, gamma=2.0, alpha=0.25, loss_weight=1.0),
+                 loss_bbox=dict(type="L1Loss", loss_weight=1.0),
+                 test_cfg=dict(nms_pre=2000, min_bbox_size=0, score_thr=0.05, nms=dict(type="nms_rotated", iou_thr=0.1),
+                               max_per_img=2000),
+                 train_cfg=_ATSS_ASSIGN):
+        # the reference class takes RotatedRetinaHead's signature as it is (MaxIoU train_cfg, 9 anchors); the defaults
+        # here are the values of its only config, configs/rotated_retinanet/..._atss.py:L16-54
+        super().__init__(num_classes=num_classes, in_channels=in_channels, feat_channels=feat_channels,
+                         stacked_convs=stacked_convs, octave_base_scale=octave_base_scale,
+                         scales_per_octave=scales_per_octave, anchor_ratios=anchor_ratios,
+                         anchor_strides=anchor_strides, anchor_base_sizes=anchor_base_sizes, target_means=target_means,
+                         target_stds=target_stds, loss_cls=loss_cls, loss_bbox=loss_bbox, test_cfg=test_cfg,
+                         train_cfg=train_cfg)
+
+    def anchor_target_single(self, flat_anchors, valid_flags, num_level_anchors, gt_bboxes, gt_bboxes_ignore, gt_labels,
+                             img_meta, cfg=None, label_channels=1, sampling=True, unmap_outputs=True):
+        bbox_coder_cfg = cfg.get("bbox_coder", "")
+        if bbox_coder_cfg == "":
+            bbox_coder_cfg = dict(type="DeltaXYWHBBoxCoder")
+        bbox_coder = build_from_cfg(bbox_coder_cfg, BOXES)
+        reg_decoded_bbox = cfg.get("reg_decoded_bbox", False)
+        allowed_border = cfg.get("allowed_border", -1)
+        inside_flags = anchor_inside_flags(flat_anchors, valid_flags, img_meta["img_shape"][:2], allowed_border)
+        all_inside = allowed_border < 0 and bool(img_meta.get("_all_valid", False))
+        if not all_inside and not bool(inside_flags.any()):
+            return (None,) * 6
+        anchors = flat_anchors if all_inside else flat_anchors[inside_flags, :]
+        num_level_anchors_inside = list(num_level_anchors) if all_inside else get_num_level_anchors_inside(
+            num_level_anchors, inside_flags)
+        bbox_assigner = build_from_cfg(cfg.get("assigner", ""), BOXES)
+        assign_result = bbox_assigner.assign(anchors, num_level_anchors_inside, gt_bboxes, gt_bboxes_ignore, gt_labels)
+        if sampling:
+            bbox_sampler = build_from_cfg(cfg.get("sampler", ""), BOXES)
+            sampling_result = bbox_sampler.sample(assign_result, anchors, gt_bboxes, gt_labels)
+        else:
+            sampling_result = PseudoSampler().sample(assign_result, anchors, gt_bboxes)
+
+        num_valid_anchors = anchors.shape[0]
+        bbox_targets = torch.zeros_like(anchors)
+        bbox_weights = torch.zeros_like(anchors)
+        labels = torch.zeros((num_valid_anchors,), dtype=torch.int32, device=anchors.device)
+        label_weights = torch.zeros((num_valid_anchors,), dtype=torch.float32, device=anchors.device)
+        pos_inds, neg_inds = sampling_result.pos_inds, sampling_result.neg_inds
+        if len(pos_inds) > 0:
+            if not reg_decoded_bbox:
+                pos_bbox_targets = bbox_coder.encode(sampling_result.pos_bboxes, sampling_result.pos_gt_bboxes)
+            else:
+                pos_bbox_targets = sampling_result.pos_gt_bboxes
+            bbox_targets[pos_inds, :] = pos_bbox_targets.to(bbox_targets.dtype)
+            bbox_weights[pos_inds, :] = 1.0
+            if gt_labels is None:
+                labels[pos_inds] = 1
+            else:
+                labels[pos_inds] = gt_labels[sampling_result.pos_assigned_gt_inds].to(labels.dtype)
+            pos_weight = cfg.get("pos_weight", -1)
+            label_weights[pos_inds] = 1.0 if pos_weight <= 0 else pos_weight
+        if len(neg_inds) > 0:
+            label_weights[neg_inds] = 1.0
+        if unmap_outputs and not all_inside:
+            num_total_anchors = flat_anchors.size(0)
+            labels = unmap(labels, num_total_anchors, inside_flags)
+            label_weights = unmap(label_weights, num_total_anchors, inside_flags)
+            bbox_targets = unmap(bbox_targets, num_total_anchors, inside_flags)
+            bbox_weights = unmap(bbox_weights, num_total_anchors, inside_flags)
+        return (labels, label_weights, bbox_targets, bbox_weights, pos_inds, neg_inds)
+
+    @staticmethod
+    def _dense_ok(cfg, sampling, img_metas, gt_bboxes_ignore_list, anchors):
+        if sampling or cfg.get("allowed_border", -1) >= 0:
+            return False
+        if not all(bool(m.get("_all_valid", False)) for m in img_metas):
+            return False
+        if any(g is not None and g.numel() > 0 for g in gt_bboxes_ignore_list):
+            return False
+        coder, assigner = cfg.get("bbox_coder", ""), cfg.get("assigner", "")
+        if assigner == "" or assigner.get("type") != "ATSSAssignerRbbox":
+            return False
+        if not cfg.get("reg_decoded_bbox", False) and (coder == "" or coder.get("type") != "DeltaXYWHABBoxCoder"):
+            return False
+        return anchors.is_cuda and anchors.shape[-1] == 5 and anchors.dtype == torch.float32
+
+    def anchor_target(self, anchor_list, valid_flag_list, gt_bboxes_list, img_metas, target_means, target_stds, cfg,
+                      gt_bboxes_ignore_list=None, gt_labels_list=None, label_channels=1, sampling=True,
+                      unmap_outputs=True, dense=True):
+        num_imgs = len(img_metas)
+        assert len(anchor_list) == len(valid_flag_list) == num_imgs
+        num_level_anchors = [anchors.size(0) for anchors in anchor_list[0]]
+        for i in range(num_imgs):
+            assert len(anchor_list[i]) == len(valid_flag_list[i])
+            anchor_list[i] = torch.cat(anchor_list[i])
+            valid_flag_list[i] = torch.cat(valid_flag_list[i])
+        if gt_bboxes_ignore_list is None:
+            gt_bboxes_ignore_list = [None for _ in range(num_imgs)]
+        if gt_labels_list is None:
+            gt_labels_list = [None for _ in range(num_imgs)]
+        if dense and self._dense_ok(cfg, sampling, img_metas, gt_bboxes_ignore_list, anchor_list[0]):
+            assigner = build_from_cfg(cfg.get("assigner", ""), BOXES)
+            labels, label_weights, bbox_targets, bbox_weights, npos = dense_targets(
+                anchor_list, gt_bboxes_list, gt_labels_list, cfg,
+                lambda anchors, gt: assigner.assign(anchors, num_level_anchors, gt).gt_inds)
+            split = lambda t: list(torch.split(t, num_level_anchors, dim=1))  # noqa: E731
+            return (split(labels), split(label_weights), split(bbox_targets), split(bbox_weights), npos, 0)
+        num_level_anchors_list = [num_level_anchors] * num_imgs
+        (all_labels, all_label_weights, all_bbox_targets, all_bbox_weights, pos_inds_list, neg_inds_list) = multi_apply(
+            self.anchor_target_single, anchor_list, valid_flag_list, num_level_anchors_list, gt_bboxes_list,
+            gt_bboxes_ignore_list, gt_labels_list, img_metas, cfg=cfg, label_channels=label_channels,
+            sampling=sampling, unmap_outputs=unmap_outputs)
+        if any([labels is None for labels in all_labels]):
+            return None
+        num_total_pos = sum([max(inds.numel(), 1) for inds in pos_inds_list])
+        num_total_neg = sum([max(inds.numel(), 1) for inds in neg_inds_list])
+        labels_list = images_to_levels(all_labels, num_level_anchors)
+        label_weights_list = images_to_levels(all_label_weights, num_level_anchors)
+        bbox_targets_list = images_to_levels(all_bbox_targets, num_level_anchors)
+        bbox_weights_list = images_to_levels(all_bbox_weights, num_level_anchors)
+        return (labels_list, label_weights_list, bbox_targets_list, bbox_weights_list, num_total_pos, num_total_neg)
+
+    def loss(self, cls_scores, bbox_preds, gt_bboxes, gt_labels, img_metas, gt_bboxes_ignore=None):
+        cfg = self.train_cfg.copy()
+        featmap_sizes = [tuple(featmap.shape[-2:]) for featmap in cls_scores]
+        assert len(featmap_sizes) == len(self.anchor_generators)
+        anchor_list, valid_flag_list = self.get_init_anchors(featmap_sizes, img_metas, cls_scores[0].device)
+        num_level_anchors = [anchors.size(0) for anchors in anchor_list[0]]
+        concat_anchor_list = [torch.cat(anchor_list[i]) for i in range(len(anchor_list))]
+        all_anchor_list = images_to_levels(concat_anchor_list, num_level_anchors)
+        label_channels = self.cls_out_channels if self.use_sigmoid_cls else 1
+        cls_reg_targets = self.anchor_target(anchor_list, valid_flag_list, gt_bboxes, img_metas, self.target_means,
+                                             self.target_stds, cfg, gt_bboxes_ignore_list=gt_bboxes_ignore,
+                                             gt_labels_list=gt_labels, label_channels=label_channels,
+                                             sampling=self.sampling)
+        if cls_reg_targets is None:
+            return None
+        labels_list, label_weights_list, bbox_targets_list, bbox_weights_list, num_total_pos, num_total_neg = \
+            cls_reg_targets
+        num_total_samples = num_total_pos + num_total_neg if self.sampling else num_total_pos
+        losses_cls, losses_bbox = multi_apply(self.loss_single, cls_scores, bbox_preds, all_anchor_list, labels_list,
+                                              label_weights_list, bbox_targets_list, bbox_weights_list,
+                                              num_total_samples=num_total_samples, cfg=cfg)
+        return dict(loss_cls=losses_cls, loss_bbox=losses_bbox)

@@ -1,0 +1,159 @@
+"""numpy restatement of ATSSAssignerRbbox.assign (python/jdet/models/boxes/assigner.py:L314-391 of the reference) with
+the rules include/jdet_hip_atss.h fixes where the reference leaves them open, and the fixtures of the ATSS tests.
+
+What is fp32 here, in the stated order, is what the kernel computes in fp32: the centre distance
+sqrt(dx*dx + dy*dy), the serial sums of mean and unbiased variance, sqrt(max(var, 1e-6)) and the `>=` compare.  The IoU
+comes from oracle.box_iou_rotated (version 0, sort mode 0), bit-equal to the device kernel
+(tests/test_gpu_iou_nms.py).  The inside test is the reference's LITERAL route (L734-740: atan2 of the offset, cos /
+sin of the angle difference) in float64 -- not the kernel's algebraic fp32 form; `margin` says how far every candidate
+is from the edge where the two could disagree.
+
+Pinned by restatement only: Jittor is not importable here, and its `topk` / `argmax` tie orders are not pinned by
+anything; lower anchor index / lower gt index are this project's rules."""
+import math
+
+import numpy as np
+
+F32 = np.float32
+NEG_INF = F32(-1e8)          # L374: INF = 100000000
+
+
+def level_offsets(num_level):
+    return np.concatenate([[0], np.cumsum(num_level)]).astype(np.int32)
+
+
+def candidates(anchors, num_level, gts, topk):
+    """(K, C) anchor indices, level-major then rank (smallest distance first, ties to the lower index), and the number
+    of distance ties across a level's rank k / k+1 boundary"""
+    a, g = np.asarray(anchors, F32), np.asarray(gts, F32)
+    dx = a[:, None, 0] - g[None, :, 0]
+    dy = a[:, None, 1] - g[None, :, 1]
+    dist = np.sqrt(dx * dx + dy * dy)                    # fp32, every operation rounded
+    assert dist.dtype == F32
+    offs = level_offsets(num_level)
+    cols, ties = [], 0
+    for l in range(len(num_level)):
+        lo, hi = int(offs[l]), int(offs[l + 1])
+        k = min(topk, hi - lo)
+        if k <= 0:
+            continue
+        order = np.argsort(dist[lo:hi], axis=0, kind="stable")      # stable: equal distances keep index order
+        cols.append(order[:k] + lo)
+        if hi - lo > k:
+            d = np.take_along_axis(dist[lo:hi], order, 0)
+            ties += int((d[k - 1] == d[k]).sum())
+    return np.concatenate(cols, 0).T.copy(), ties
+
+
+def inside_literal64(points, rrects):
+    """points_in_rotated_boxes (boxes/box_ops.py:L725-741) as written, in float64: flags (n, m) and the distances of
+    delta_w / delta_h from w/2 / h/2 relative to (w/2 + 1) / (h/2 + 1)"""
+    p, r = np.asarray(points, np.float64), np.asarray(rrects, np.float64)
+    off = p[:, None, :2] - r[None, :, :2]
+    ang = np.arctan2(off[..., 1], off[..., 0])
+    d = np.sqrt((off ** 2).sum(-1))
+    da = ang - r[None, :, 4]
+    dw, dh = np.abs(d * np.cos(da)), np.abs(d * np.sin(da))
+    hw, hh = r[None, :, 2] / 2, r[None, :, 3] / 2
+    margin = np.minimum(np.abs(dw - hw) / (hw + 1), np.abs(dh - hh) / (hh + 1))
+    return (dw < hw) & (dh < hh), margin
+
+
+def iou_matrix(anchors, gts):
+    from oracle import oracle as O
+    return O.box_iou_rotated(np.ascontiguousarray(anchors, F32)[:, :5].copy(), np.ascontiguousarray(gts, F32), 0, 0)
+
+
+def assign(anchors, num_level, gts, topk, gt_labels=None, labels_filled=0, overlaps=None):
+    """-> dict(gt_inds int32 (A), max_overlaps fp32 (A), labels int32 (A) | None, and the facts the tests ask of a
+    fixture: margin, boundary_ties, positives_per_gt, multi_claimed, cand, thr)"""
+    a, g = np.asarray(anchors, F32)[:, :5], np.asarray(gts, F32)
+    A, K = a.shape[0], g.shape[0]
+    if A == 0 or K == 0:
+        raise ValueError("No gt or bboxes")
+    ov = iou_matrix(a, g) if overlaps is None else np.asarray(overlaps, F32)
+    assert ov.shape == (A, K) and ov.dtype == F32
+    cand, ties = candidates(a, num_level, g, topk)
+    C = cand.shape[1]
+    assert C >= 2
+    gi = np.arange(K)
+    civ = ov[cand, gi[:, None]]                           # (K, C)
+    thr = np.empty(K, F32)
+    for k in range(K):
+        s = F32(0)
+        for c in range(C):
+            s = F32(s + civ[k, c])
+        mean = F32(s / F32(C))
+        v = F32(0)
+        for c in range(C):
+            d = F32(civ[k, c] - mean)
+            v = F32(v + F32(d * d))
+        var = F32(v / F32(C - 1))
+        thr[k] = F32(mean + F32(np.sqrt(np.maximum(var, F32(1e-6)))))
+    flags, margin = inside_literal64(a[:, :2], g)
+    inside = flags[cand, gi[:, None]]
+    pos = (civ >= thr[:, None]) & inside & (civ > 0)
+    # the highest IoU wins, equal IoUs go to the lower gt index (first maximum)
+    best = np.full(A, NEG_INF, F32)
+    owner = np.zeros(A, np.int32)
+    claims = np.zeros(A, np.int32)
+    for k in range(K):                                    # ascending gt index, strict >: the first maximum stays
+        for c in np.flatnonzero(pos[k]):
+            j = cand[k, c]
+            claims[j] += 1
+            if civ[k, c] > best[j]:
+                best[j], owner[j] = civ[k, c], k + 1
+    labels = None
+    if gt_labels is not None:
+        gl = np.asarray(gt_labels, np.int32)
+        labels = np.where(owner > 0, gl[np.maximum(owner - 1, 0)], np.int32(labels_filled)).astype(np.int32)
+    return dict(gt_inds=owner, max_overlaps=best, labels=labels, cand=cand, thr=thr,
+                margin=float(margin[cand, gi[:, None]].min()), boundary_ties=ties,
+                positives_per_gt=pos.sum(1), multi_claimed=int((claims > 1).sum()))
+
+
+# ---- fixtures ------------------------------------------------------------------------------------------------------
+STRIDES = (8, 16, 32, 64, 128)
+# (image size, K, seed): 256 -> A = 1364, levels 1024 / 256 / 64 / 16 / 4 (the last below topk: C = 40);
+# 512 -> A = 5456, C = 45.  Seeds chosen so that every fixture holds the conditions of tests/test_atss_cpu.py.
+FIXTURES = {"256a": (256, 8, 0), "256b": (256, 8, 4), "512a": (512, 16, 0), "512b": (512, 16, 1)}
+TOPK = 9
+
+
+def lattice(size):
+    """anchors (A, 5) fp32 of the config's generator (octave_base_scale 4, one scale per octave, ratio 1, angle 0) on a
+    size x size image, and the anchors per level"""
+    from jdet_amd.models.boxes.anchor_generator import AnchorGeneratorRotatedRetinaNet
+    levels = []
+    for s in STRIDES:
+        gen = AnchorGeneratorRotatedRetinaNet(s, None, [1.0], octave_base_scale=4, scales_per_octave=1)
+        f = int(math.ceil(size / s))
+        levels.append(gen.grid_anchors((f, f), s, device="cpu").numpy().astype(F32))
+    return np.concatenate(levels, 0), [lv.shape[0] for lv in levels]
+
+
+def random_gts(rng, size, K):
+    """centres uniform in the middle 80 % of the image, sides log-uniform in [16, 0.6 * size], angle uniform in
+    +-pi/2"""
+    c = rng.uniform(0.1 * size, 0.9 * size, (K, 2))
+    wh = np.exp(rng.uniform(math.log(16.0), math.log(0.6 * size), (K, 2)))
+    th = rng.uniform(-math.pi / 2, math.pi / 2, (K, 1))
+    return np.concatenate([c, wh, th], 1).astype(F32)
+
+
+_CACHE = {}
+
+
+def fixture(name):
+    """(anchors, num_level, gts, gt_labels, restatement result) of a named fixture; computed once, never modified"""
+    if name not in _CACHE:
+        size, K, seed = FIXTURES[name]
+        rng = np.random.default_rng(seed)
+        anchors, num_level = lattice(size)
+        gts = random_gts(rng, size, K)
+        labels = rng.integers(1, 16, K).astype(np.int32)
+        ref = assign(anchors, num_level, gts, TOPK, labels, 0)
+        for v in (anchors, gts, labels):
+            v.setflags(write=False)
+        _CACHE[name] = (anchors, num_level, gts, labels, ref)
+    return _CACHE[name]
