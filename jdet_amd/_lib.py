@@ -155,6 +155,17 @@ ATSS_SIGNATURES = {
     "jdet_atss_assign": (_i, [_p, _i, _i, _p, _i, _p, _i, _p, _p, _i, _i, _p, _p, _p, _p, _sz, _p]),
 }
 
+# include/jdet_hip_rows.h (csrc/conv_rows.hip; same library, a table of its own for the reason ATSS_SIGNATURES has one;
+# tests/test_conv_rows_cpu.py checks it against the header and the exports)
+ROWS_SIGNATURES = {
+    "jdet_rows_nonzero_workspace": (_sz, [_i, _i, _i]),
+    "jdet_rows_nonzero": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _sz, _p]),
+    "jdet_conv3x3_rows_supported": (_i, [_i, _i]),
+    "jdet_conv3x3_wgrad_rows_workers": (_i, [_i, _i]),
+    "jdet_conv3x3_wgrad_rows": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p]),
+    "jdet_conv3x3_dgrad_rows": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p]),
+}
+
 _lib = None
 
 # Hull-point ordering inside the rotated IoU: 0 = the reference's CPU path (std::sort,
@@ -185,7 +196,7 @@ def lib():
         # process and our DT_NEEDED entry resolves to that same runtime: one HIP context, shared
         # streams and allocations.
         l = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(ATSS_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(ATSS_SIGNATURES.items()) + list(ROWS_SIGNATURES.items()):
             fn = getattr(l, name)  # AttributeError here == ABI drift: fail loudly
             fn.restype = res
             fn.argtypes = args

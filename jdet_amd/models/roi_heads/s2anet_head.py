@@ -138,6 +138,11 @@ class S2ANetHead(RotatedAnchorHeadMixin, nn.Module):
             self.odm_cls_convs.append(ConvModule(chn, self.feat_channels, 3, stride=1, padding=1))
         self.odm_cls = nn.Conv2d(self.feat_channels, self.cls_out_channels, 3, padding=1)
         self.odm_reg = nn.Conv2d(self.feat_channels, 5, 3, padding=1)
+        # the regression branches are trained by a smooth-L1 loss that weighs only the positive anchors: the gradient
+        # entering their towers is zero on almost every position row (gap rows of a LevelPack included), on the
+        # per-level and on the packed path alike -- their backward takes the non-zero rows (profiles/conv_rows.md)
+        for m in list(self.fam_reg_convs) + list(self.odm_reg_convs):
+            m.row_sparse_grad = True
         self.init_weights()
 
     def init_weights(self):

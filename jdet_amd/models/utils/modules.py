@@ -23,6 +23,10 @@ class ConvModule(nn.Module):
         assert act_cfg is None or isinstance(act_cfg, dict)
         assert isinstance(order, tuple) and set(order) == {"conv", "norm", "act"}
         self.order = order
+        # routing hint for the fused 3x3 path: the gradient reaching this layer is zero on most position rows (a tower
+        # under a loss that weighs only the positive anchors), take its backward from the non-zero rows
+        # (ops/conv_igemm._rows_backward).  Any gradient is computed correctly either way.
+        self.row_sparse_grad = False
         self.with_norm = norm_cfg is not None
         self.with_activation = act_cfg is not None
         if bias == "auto":
@@ -71,7 +75,7 @@ class ConvModule(nn.Module):
             return None
         if not (x.is_cuda and x.dtype == conv.weight.dtype) or torch.is_autocast_enabled():
             return None      # (autocast: the framework path casts per op; the fused route is fp32 only)
-        return conv_igemm.conv_module(conv, x, relu)
+        return conv_igemm.conv_module(conv, x, relu, self.row_sparse_grad)
 
     def masked(self, x, rowmask):
         """relu(conv(x)) * mask as one kernel (mask: 0 / 1 per position, flat) when this is a plain conv + bias + ReLU
@@ -80,7 +84,7 @@ class ConvModule(nn.Module):
                 or self.order.index("conv") > self.order.index("act") or type(self.conv) is not nn.Conv2d
                 or not (x.is_cuda and x.dtype == self.conv.weight.dtype)):
             return None
-        return conv_igemm.masked_conv_module(self.conv, x, rowmask)
+        return conv_igemm.masked_conv_module(self.conv, x, rowmask, self.row_sparse_grad)
 
     def forward(self, x, activate=True, norm=True):
         y = self._fused_conv_relu(x, activate)

@@ -89,10 +89,11 @@ def wgrad_supported(cin, cout):
     return bool(L.lib().jdet_conv3x3_wgrad_supported(int(cin), int(cout)))
 
 
-def conv3x3_wgrad_nhwc(x_nhwc, gy_nhwc, offset=None, out=None, ksplit=0):
+def conv3x3_wgrad_nhwc(x_nhwc, gy_nhwc, offset=None, out=None, ksplit=0, rows=None):
     """x (N,H,W,Cin), gy (N,H,W,Cout) contiguous fp32 [offset (N,18,H,W): the deformable form] -> the weight gradient
     (Cout,3,3,Cin).  `out`: a contiguous (Cout,3,3,Cin) buffer the gradient is ADDED to (csrc/conv_wgrad.hip), else a
-    fresh zero-filled one."""
+    fresh zero-filled one.  `rows`: (int32 device list of the non-zero rows of gy, device address of its count) -- the
+    sum then runs over those rows only (csrc/conv_rows.hip: jdet_conv3x3_wgrad_rows; plain form)."""
     L.need_device(x_nhwc, gy_nhwc, offset, out)
     N, H, W, Cin = x_nhwc.shape
     Cout = gy_nhwc.shape[3]
@@ -105,7 +106,7 @@ def conv3x3_wgrad_nhwc(x_nhwc, gy_nhwc, offset=None, out=None, ksplit=0):
         out = torch.zeros((Cout, 3, 3, Cin), dtype=torch.float32, device=x_nhwc.device)
     elif tuple(out.shape) != (Cout, 3, 3, Cin) or not out.is_contiguous() or out.dtype != torch.float32:
         raise ValueError("out must be a contiguous fp32 (Cout, 3, 3, Cin) tensor")
-    L.check(_wgrad_call(x_nhwc, gy_nhwc, offset, N, H, W, Cin, Cout, L.ptr(out), ksplit), "jdet_conv3x3_wgrad")
+    L.check(_wgrad_call(x_nhwc, gy_nhwc, offset, N, H, W, Cin, Cout, L.ptr(out), ksplit, rows), "jdet_conv3x3_wgrad")
     return out
 
 
@@ -129,7 +130,12 @@ def conv3x3_wgrad(x, gy, offset=None, ksplit=0):
 # its favour), 744 -> 727 launches (18 library zero fills and 8 accumulation adds fewer): profiles/r06_conv_prefetch.md.
 # JDET_CONV_WGRAD=0: the library's.
 WGRAD = os.environ.get("JDET_CONV_WGRAD", "1") == "1"
-def _wgrad_call(x_nhwc, gy_nhwc, offset, N, H, W, Cin, Cout, out_ptr, ksplit):
+def _wgrad_call(x_nhwc, gy_nhwc, offset, N, H, W, Cin, Cout, out_ptr, ksplit, rows=None):
+    if rows is not None:
+        if offset is not None:
+            raise ValueError("the row list belongs to the plain form")
+        return L.lib().jdet_conv3x3_wgrad_rows(L.ptr(x_nhwc), L.ptr(gy_nhwc), L.ptr(rows[0]), rows[1], N, H, W, Cin, Cout,
+                                               out_ptr, L.stream_ptr(x_nhwc))
     return L.lib().jdet_conv3x3_wgrad(L.ptr(x_nhwc), L.ptr(gy_nhwc), L.ptr(L.f32c(offset)) if offset is not None else None,
                                       N, H, W, Cin, Cout, out_ptr, int(ksplit), L.stream_ptr(x_nhwc))
 
@@ -137,8 +143,9 @@ def _wgrad_call(x_nhwc, gy_nhwc, offset, N, H, W, Cin, Cout, out_ptr, ksplit):
 _GW_ACC = {}           # weight.data_ptr() -> (backward pass id, device pointer of the (Cout,3,3,Cin) buffer, its shape)
 
 
-def shared_wgrad(weight, x_nhwc, gy_nhwc, offset=None):
-    """weight gradient of y = conv3x3(x, weight) [deformable with `offset`] for this use of `weight`, as autograd wants
+def shared_wgrad(weight, x_nhwc, gy_nhwc, offset=None, rows=None):
+    """weight gradient of y = conv3x3(x, weight) [deformable with `offset`; `rows`: see conv3x3_wgrad_nhwc -- dense and
+    row-list uses of one weight share the buffer like any others] for this use of `weight`, as autograd wants
     it: the first use in a backward pass returns a fresh (Cout, Cin, 3, 3) tensor (channels_last memory, so a
     channels_last parameter takes it without a copy); later uses add into that tensor's memory and return None.  Only
     the pointer is remembered -- a second reference would make AccumulateGrad clone the gradient instead of taking it."""
@@ -155,9 +162,9 @@ def shared_wgrad(weight, x_nhwc, gy_nhwc, offset=None):
     if tid >= 0 and hit is not None and hit[0] == tid and hit[2] == (Cout, Cin, x_nhwc.device):
         N, H, W, _ = x_nhwc.shape
         x_nhwc, gy_nhwc = L.f32c(x_nhwc), L.f32c(gy_nhwc)
-        L.check(_wgrad_call(x_nhwc, gy_nhwc, offset, N, H, W, Cin, Cout, hit[1], 0), "jdet_conv3x3_wgrad")
+        L.check(_wgrad_call(x_nhwc, gy_nhwc, offset, N, H, W, Cin, Cout, hit[1], 0, rows), "jdet_conv3x3_wgrad")
         return None
-    buf = conv3x3_wgrad_nhwc(x_nhwc, gy_nhwc, offset)
+    buf = conv3x3_wgrad_nhwc(x_nhwc, gy_nhwc, offset, rows=rows)
     if tid >= 0 and (_GW_ACC.get(key) is None or _GW_ACC[key][0] != tid):
         _GW_ACC[key] = (tid, buf.data_ptr(), (Cout, Cin, x_nhwc.device), stream)
     return buf.permute(0, 3, 1, 2)
@@ -266,6 +273,110 @@ def bias_act_backward(g, y, relu):
     return gp.permute(0, 3, 1, 2), gb
 
 
+# Row-sparse backward of the regression towers (csrc/conv_rows.hip, profiles/conv_rows.md): a layer whose ConvModule
+# carries `row_sparse_grad` takes its data and weight gradients from the non-zero rows of the incoming gradient.  The flag
+# is a routing hint only: any gradient is computed correctly, a dense one just slower.  JDET_CONV_ROWS=0: the dense
+# kernels (A/B).
+ROWS = os.environ.get("JDET_CONV_ROWS", "1") == "1"
+_ROWS_WS = {}
+
+
+def wgrad_rows_workers(cin, cout):
+    """how many workgroups at most add a partial sum to one element of gw per call (jdet_conv3x3_wgrad_rows_workers)"""
+    return int(L.lib().jdet_conv3x3_wgrad_rows_workers(int(cin), int(cout)))
+
+
+def rows_supported(cin, cout):
+    return bool(L.lib().jdet_conv3x3_rows_supported(int(cin), int(cout)))
+
+
+def _rows_scratch(nbytes, device):
+    """bias_act_backward's rule: cached per (device, stream) in eager mode, from the capturing graph's pool under capture"""
+    if torch.cuda.is_current_stream_capturing():
+        return torch.empty((nbytes,), dtype=torch.uint8, device=device)
+    key = (device.index, torch.cuda.current_stream(device).cuda_stream)
+    ws = _ROWS_WS.get(key)
+    if ws is None or ws.numel() < nbytes:
+        while len(_ROWS_WS) >= 8:
+            _ROWS_WS.pop(next(iter(_ROWS_WS)))
+        ws = _ROWS_WS[key] = torch.empty((max(nbytes, 1 << 20),), dtype=torch.uint8, device=device)
+    return ws
+
+
+def rows_nonzero(g_nhwc, scratch=None):
+    """g (N,H,W,C) contiguous fp32 -> (flags (P,) uint8, rows (P,) int32, rows_dilated (P,) int32, counts (2,) int32):
+    the rows of g that hold anything but +-0, ascending, and their 3x3 dilation inside each image; list entries past
+    their count are -1.  Everything stays on the device (csrc/conv_rows.hip: jdet_rows_nonzero).  The four
+    results are views of ONE scratch buffer that the next call on this stream reuses."""
+    L.need_device(g_nhwc)
+    N, H, W, C = g_nhwc.shape
+    P = N * H * W
+    g_nhwc = L.f32c(g_nhwc)
+    wsb = L.lib().jdet_rows_nonzero_workspace(N, H, W)
+    total = 8 * P + 16 + wsb + P            # rows | rows_dilated | counts (padded to 16) | workspace (16 n) | flags
+    buf = _rows_scratch(total, g_nhwc.device) if scratch is None else scratch
+    rows = buf[:4 * P].view(torch.int32)
+    drows = buf[4 * P:8 * P].view(torch.int32)
+    counts = buf[8 * P:8 * P + 8].view(torch.int32)
+    ws = buf[8 * P + 16:8 * P + 16 + wsb]
+    flags = buf[8 * P + 16 + wsb:total]
+    L.check(L.lib().jdet_rows_nonzero(L.ptr(g_nhwc), N, H, W, C, L.ptr(flags), L.ptr(rows), L.ptr(drows), L.ptr(counts),
+                                      L.ptr(ws), wsb, L.stream_ptr(g_nhwc)), "jdet_rows_nonzero")
+    return flags, rows, drows, counts
+
+
+def conv3x3_dgrad_rows_nhwc(gy_nhwc, wd_crsk, rows, count_ptr, out=None):
+    """gy (N,H,W,Cout), wd (Cin,3,3,Cout) flipped weights, rows: int32 device list (the dilation of gy's non-zero rows),
+    count_ptr: device address of its length -> gx (N,H,W,Cin): the listed rows computed, all others zero.  `out`: only
+    its listed rows are written."""
+    L.need_device(gy_nhwc, wd_crsk, rows, out)
+    N, H, W, Cout = gy_nhwc.shape
+    Cin = wd_crsk.shape[0]
+    if tuple(wd_crsk.shape) != (Cin, 3, 3, Cout) or not wd_crsk.is_contiguous():
+        raise ValueError("wd must be a contiguous (Cin, 3, 3, Cout) tensor, got %r" % (tuple(wd_crsk.shape),))
+    gy_nhwc = L.f32c(gy_nhwc)
+    zero = out is None
+    if zero:
+        out = torch.empty((N, H, W, Cin), dtype=torch.float32, device=gy_nhwc.device)
+    L.check(L.lib().jdet_conv3x3_dgrad_rows(L.ptr(gy_nhwc), L.ptr(wd_crsk), L.ptr(rows), count_ptr, N, H, W, Cin, Cout,
+                                            int(zero), L.ptr(out), L.stream_ptr(gy_nhwc)), "jdet_conv3x3_dgrad_rows")
+    return out
+
+
+def _rows_dgrad_weight(weight):
+    """the (Cin, 3, 3, Cout) flipped weights for the rows data gradient.  Eager: `dgrad_weight`'s bank (one launch rewrites
+    every weight in it), refreshed ONCE PER BACKWARD PASS whatever the version counters say -- the fused multi-tensor SGD
+    step (optims/optimizer.py) updates parameters without moving `_version`.  Under graph capture the flip is part of the
+    captured pass and its result lives in the graph's pool: nothing a replay reads can be freed or go stale outside it."""
+    if torch.cuda.is_current_stream_capturing() or not weight.is_cuda:
+        return weight.detach().flip(2, 3).permute(1, 2, 3, 0).contiguous()
+    wd = dgrad_weight(weight)                       # (builds / extends the bank; refreshes it if a version moved)
+    st = _DGRAD_BANKS.get(weight.device)
+    if st is None or st["bank"] is None or id(weight) not in st["items"]:
+        return dgrad_weight_fresh(weight)           # not a bank weight (layout, dtype): the per-weight form, recomputed
+    tid = torch._C._current_graph_task_id()
+    if tid < 0 or st.get("pass") != tid:
+        st["bank"].refresh()
+        st["pass"] = tid
+    return wd
+
+
+def dgrad_weight_fresh(weight):
+    return weight.detach().flip(2, 3).permute(1, 2, 3, 0).contiguous()
+
+
+def _rows_backward(g, x, weight, need_x, need_w):
+    """(grad_x, grad_w) of a plain 3x3 / stride 1 / pad 1 convolution from the non-zero rows of g (N, Cout, H, W)"""
+    gn, xn = L.f32c(g.permute(0, 2, 3, 1)), L.f32c(x.permute(0, 2, 3, 1))
+    _, rows, drows, counts = rows_nonzero(gn)
+    gx = gw = None
+    if need_w:
+        gw = shared_wgrad(weight, xn, gn, rows=(rows, counts.data_ptr()))
+    if need_x:
+        gx = conv3x3_dgrad_rows_nhwc(gn, _rows_dgrad_weight(weight), drows, counts.data_ptr() + 4).permute(0, 3, 1, 2)
+    return gx, gw
+
+
 CONV1X1_GEMM = os.environ.get("JDET_CONV1X1_GEMM", "1") == "1"
 
 
@@ -278,10 +389,11 @@ def _is_1x1(x, weight, stride, padding, groups):
 class _ConvBiasAct(torch.autograd.Function):
     """y = [relu](conv(x, w) + b).  Forward: the implicit-GEMM kernel (`igemm`: 3x3 / stride 1 / pad 1 only) or the
     library convolution; backward: bias gradient and ReLU mask in one pass (`bias_act_backward`), then the library's
-    data / weight gradients (with DGRAD, for the igemm shapes: grad_x by the igemm kernel on the flipped weights)."""
+    data / weight gradients (with DGRAD, for the igemm shapes: grad_x by the igemm kernel on the flipped weights).
+    `row_sparse` (igemm layers): both gradients from the non-zero rows of the incoming gradient (`_rows_backward`)."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, relu, stride, padding, dilation, groups, igemm, rowmask=None):
+    def forward(ctx, x, weight, bias, relu, stride, padding, dilation, groups, igemm, rowmask=None, row_sparse=False):
         # rowmask (igemm + ReLU only): the finished rows are multiplied by a 0 / 1 mask per position (the gap rows of a
         # LevelPack).  It needs no backward of its own: a masked row of y is 0, so the ReLU mask [y > 0] of
         # bias_act_backward already zeroes the gradient there.
@@ -304,6 +416,7 @@ class _ConvBiasAct(torch.autograd.Function):
             if relu:
                 y = torch.relu_(y)
         ctx.k1 = k1
+        ctx.row_sparse = bool(row_sparse) and bool(igemm)
         ctx.cfg = (bool(relu), list(stride), list(padding), list(dilation), groups, bool(igemm), bias is not None)
         ctx.save_for_backward(x, weight, y if relu else None)
         return y
@@ -340,7 +453,12 @@ class _ConvBiasAct(torch.autograd.Function):
                 # (Cout, Cin, 1, 1) is one memory order under two stride spellings: the parameter's own keeps the
                 # gradient layout contract (DDP's bucket views otherwise copy and warn)
                 gw = gw.as_strided(weight.shape, weight.stride())
-            return gx, gw, gb, None, None, None, None, None, None, None
+            return gx, gw, gb, None, None, None, None, None, None, None, None
+        if (ctx.row_sparse and ROWS and (need[0] or need[1]) and g.is_cuda and g.dtype == torch.float32
+                and rows_supported(weight.shape[1], weight.shape[0])
+                and (g.shape[0] * g.shape[2] * g.shape[3] + 16) * max(weight.shape[0], weight.shape[1]) < 2 ** 30):
+            gx, gw = _rows_backward(g, x, weight, need[0], need[1])
+            return gx, gw, gb, None, None, None, None, None, None, None, None
         if need[0] and igemm and DGRAD and supported(weight.shape[0], weight.shape[1]):
             gx = conv3x3_nhwc(L.f32c(g.permute(0, 2, 3, 1)), dgrad_weight(weight)).permute(0, 3, 1, 2)
             need[0] = False
@@ -350,18 +468,18 @@ class _ConvBiasAct(torch.autograd.Function):
             need[1] = False
         lx, lw, _ = torch.ops.aten.convolution_backward(g, x, weight, None, stride, padding, dilation, False, [0, 0],
                                                         groups, need) if any(need) else (None, None, None)
-        return (gx if gx is not None else lx), (gw if own_gw else lw), gb, None, None, None, None, None, None, None
+        return (gx if gx is not None else lx), (gw if own_gw else lw), gb, None, None, None, None, None, None, None, None
 
 
 _Conv3x3BiasAct = _ConvBiasAct      # (name used by the round-3 notes)
 
 
-def conv3x3_bias_act(x, weight, bias=None, relu=False, rowmask=None):
+def conv3x3_bias_act(x, weight, bias=None, relu=False, rowmask=None, row_sparse=False):
     """(N, Cin, H, W) logical (channels_last memory is free) -> (N, Cout, H, W) channels_last; differentiable.
     rowmask: (N*H*W,) 0 / 1 floats multiplied into the finished rows (with relu=True and a bias when gradients flow:
-    see _ConvBiasAct)"""
+    see _ConvBiasAct); row_sparse: the backward takes the rows path"""
     if needs_grad(x, weight, bias):
-        return _ConvBiasAct.apply(x, weight, bias, relu, (1, 1), (1, 1), (1, 1), 1, True, rowmask)
+        return _ConvBiasAct.apply(x, weight, bias, relu, (1, 1), (1, 1), (1, 1), 1, True, rowmask, row_sparse)
     if rowmask is not None:
         return conv3x3_nhwc(L.f32c(x.permute(0, 2, 3, 1)), weight_krsc(weight), bias, relu, rowmask).permute(0, 3, 1, 2)
     return conv3x3(x, weight, bias, relu)
@@ -372,7 +490,7 @@ def _is_igemm_conv(conv):
             == ((3, 3), (1, 1), (1, 1), (1, 1), 1))
 
 
-def masked_conv_module(conv, x, rowmask):
+def masked_conv_module(conv, x, rowmask, row_sparse=False):
     """`relu(conv(x)) * mask` in ONE kernel for a plain 3x3 / stride 1 / pad 1 nn.Conv2d with a bias where the fused
     kernel applies (the towers on a LevelPack); None = not applicable here, the caller multiplies."""
     plain = (type(conv).__name__ == "Conv2d" and conv.padding_mode == "zeros" and not isinstance(conv.padding, str)
@@ -383,10 +501,10 @@ def masked_conv_module(conv, x, rowmask):
     if grad and not (BIAS_ACT_BWD and conv.bias is not None and conv.bias.requires_grad
                      and _bias_bwd_supported(conv.out_channels)):
         return None          # (the ReLU mask of the one-pass bias backward is what zeroes the masked rows' gradient)
-    return conv3x3_bias_act(x, conv.weight, conv.bias, True, rowmask)
+    return conv3x3_bias_act(x, conv.weight, conv.bias, True, rowmask, row_sparse)
 
 
-def conv_module(conv, x, relu=False):
+def conv_module(conv, x, relu=False, row_sparse=False):
     """`[relu](conv(x))` for a plain nn.Conv2d (zeros padding).  3x3 / stride 1 / pad 1 layers take the fused kernel
     when `preferred()` says so; any layer WITH a bias that needs gradients goes through `_ConvBiasAct`, whose backward
     produces the bias gradient and the ReLU mask in one pass; everything else is the library call it always was."""
@@ -397,7 +515,7 @@ def conv_module(conv, x, relu=False):
     # narrow-tile kernels keep their forward; their bias gradient still comes from the own column sum below)
     if (plain and _is_igemm_conv(conv) and conv.out_channels >= 32 and preferred(x, conv.weight)
             and (TRAIN or not grad)):
-        return conv3x3_bias_act(x, conv.weight, conv.bias, relu)
+        return conv3x3_bias_act(x, conv.weight, conv.bias, relu, None, row_sparse)
     if (plain and grad and BIAS_ACT_BWD and conv.bias is not None and x.is_cuda and x.dtype == torch.float32
             and (_bias_bwd_supported(conv.out_channels) or (not relu and conv.out_channels <= 256))):
         return _ConvBiasAct.apply(x, conv.weight, conv.bias, relu, conv.stride, conv.padding, conv.dilation,
