@@ -166,6 +166,13 @@ ROWS_SIGNATURES = {
     "jdet_conv3x3_dgrad_rows": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p]),
 }
 
+# include/jdet_hip_fcos.h (csrc/fcos_targets.hip, csrc/poly_iou_loss.hip; same library, a table of its own for the reason
+# ATSS_SIGNATURES has one; tests/test_fcos_cpu.py checks it against the header and the exports)
+FCOS_SIGNATURES = {
+    "jdet_fcos_targets": (_i, [_p, _p, _i, _p, _p, _p, _i, _i, _i, _i, _i, _f, _p, _p, _p, _p, _p]),
+    "jdet_poly_iou_loss": (_i, [_p, _p, _p, _l, _i, _f, _p, _p, _p]),
+}
+
 _lib = None
 
 # Hull-point ordering inside the rotated IoU: 0 = the reference's CPU path (std::sort,
@@ -196,7 +203,8 @@ def lib():
         # process and our DT_NEEDED entry resolves to that same runtime: one HIP context, shared
         # streams and allocations.
         l = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(ATSS_SIGNATURES.items()) + list(ROWS_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(ATSS_SIGNATURES.items()) + list(ROWS_SIGNATURES.items()) + \
+                list(FCOS_SIGNATURES.items()):
             fn = getattr(l, name)  # AttributeError here == ABI drift: fail loudly
             fn.restype = res
             fn.argtypes = args

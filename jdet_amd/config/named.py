@@ -176,6 +176,27 @@ ATSS_RETINANET_CFG = dict(
     **_SGD_1X)
 
 
+FCOS_CFG = dict(
+    # configs/fcos/fcos_obb_r50_fpn_1x_dota.py: model L2-42, optimizer L118-129.  Anchor-free: one point per location,
+    # targets by jdet_fcos_targets, box loss the polygon IoU (jdet_poly_iou_loss); GroupNorm towers (the head's default).
+    model=dict(
+        type="FCOS",
+        backbone=dict(type="Resnet50", frozen_stages=1, norm_eval=True,
+                      return_stages=["layer1", "layer2", "layer3", "layer4"], pretrained=True),
+        neck=dict(type="FPN", in_channels=[256, 512, 1024, 2048], out_channels=256, start_level=1,
+                  add_extra_convs="on_output", num_outs=5, relu_before_extra_convs=True),
+        roi_heads=dict(
+            type="FCOSHead", num_classes=15, in_channels=256, stacked_convs=4, feat_channels=256,
+            strides=[8, 16, 32, 64, 128], scale_theta=True, norm_on_bbox=True,
+            loss_cls=dict(type="FocalLoss", gamma=2.0, alpha=0.25, loss_weight=1.0),
+            loss_bbox=dict(type="PolyIoULoss", loss_weight=1.0),
+            loss_centerness=dict(type="CrossEntropyLoss", use_bce=True, loss_weight=1.0),
+            test_cfg=dict(centerness_factor=0.5, nms_pre=1000, min_bbox_size=0, score_thr=0.05,
+                          nms=dict(type="obb_nms", iou_thr=0.1), max_per_img=2000))),
+    optimizer=dict(type="SGD", lr=0.0025, momentum=0.9, weight_decay=0.0001, grad_clip=dict(max_norm=35, norm_type=2)),
+    scheduler=dict(type="StepLR", warmup="linear", warmup_iters=500, warmup_ratio=1.0 / 3, milestones=[8, 11]))
+
+
 GLIDING_CFG = dict(
     # configs/gliding_r50_fpn_1x_dota_with_flip.py: model L2-116, optimizer L195, scheduler L197-202
     # (tests/golden/configs/gliding_r50_fpn_1x_dota_with_flip.yaml holds them as `Config` reads them)

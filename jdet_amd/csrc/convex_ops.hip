@@ -20,6 +20,7 @@
 // Execution: one thread per (point set, polygon) pair resp. per point set; the work is a few hundred flops on
 // thread-private arrays, tens of thousands of pairs per call: latency-insensitive, nowhere near any roofline.
 #include "common.h"
+#include "graham_scan.h"
 
 namespace {
 
@@ -246,69 +247,10 @@ __global__ __launch_bounds__(64) void convex_sort_kernel(const float* __restrict
   if (b >= nbs) return;
   const float* p = pts + (size_t)b * npts * 2;
   const float* m = masks + (size_t)b * npts;
-  const int index_size = circular ? npts + 1 : npts;
-  int* idx = out + (size_t)b * index_size;
-  for (int i = 0; i < index_size; i++) idx[i] = -1;
-  // start: argmin of m * y + (1 - m) * 1e7, first minimum (convex_sort.py:L169-171)
-  int start = 0;
-  float best = 0.f;
-  for (int i = 0; i < npts; i++) {
-    const float v = m[i] * p[2 * i + 1] + (1 - m[i]) * 10000000.f;
-    if (i == 0 || v < best) {
-      best = v;
-      start = i;
-    }
-  }
-  const float sx = p[2 * start], sy = p[2 * start + 1];
-  // order: stable argsort of the cosine to the start point, descending (L175-176)
-  float key[kSortMax];
-  int order[kSortMax];
-  for (int i = 0; i < npts; i++) {
-    const float dx = p[2 * i] - sx, dy = p[2 * i + 1] - sy;
-    const float c = dx / sqrtf(dx * dx + dy * dy + 0.000001f);
-    int j = i;
-    while (j > 0 && key[j - 1] < c) {
-      key[j] = key[j - 1];
-      order[j] = order[j - 1];
-      j--;
-    }
-    key[j] = c;
-    order[j] = i;
-  }
-  // Graham scan (L4-65)
-  idx[0] = start;
-  int c_i = 0;
-  for (int _j = 0; _j < npts; _j++) {
-    const int j = order[_j];
-    if (j == start) continue;
-    if (m[j] < 0.5f) continue;
-    const float x0 = p[2 * j], y0 = p[2 * j + 1];
-    float x1 = p[2 * idx[c_i]], y1 = p[2 * idx[c_i] + 1];
-    const float d = (x1 - x0) * (x1 - x0) + (y1 - y0) * (y1 - y0);
-    if ((double)d < 0.000001) continue;
-    if (c_i < 2) {
-      idx[++c_i] = j;
-    } else {
-      float x2 = p[2 * idx[c_i - 1]], y2 = p[2 * idx[c_i - 1] + 1];
-      while (1) {
-        const float t = (x1 - x2) * (y0 - y2) - (y1 - y2) * (x0 - x2);
-        if (t >= 0) {
-          idx[++c_i] = j;
-          break;
-        }
-        if (c_i <= 1) {
-          idx[c_i] = j;
-          break;
-        }
-        c_i--;
-        x1 = p[2 * idx[c_i]];
-        y1 = p[2 * idx[c_i] + 1];
-        x2 = p[2 * idx[c_i - 1]];
-        y2 = p[2 * idx[c_i - 1] + 1];
-      }
-    }
-  }
-  if (circular) idx[++c_i] = idx[0];
+  int* idx = out + (size_t)b * (circular ? npts + 1 : npts);
+  // start point, angular order and scan: graham_scan.h (shared with the polygon IoU loss)
+  jdet_graham_scan<kSortMax>([&](int i) { return p[2 * i]; }, [&](int i) { return p[2 * i + 1]; },
+                             [&](int i) { return m[i]; }, npts, circular, [&](int i) -> int& { return idx[i]; });
 }
 
 }  // namespace

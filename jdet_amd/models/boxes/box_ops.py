@@ -110,3 +110,33 @@ def points_in_rotated_boxes(points, rrects):
     delta_w = torch.abs(offset_distances * torch.cos(delta_angles))
     delta_h = torch.abs(offset_distances * torch.sin(delta_angles))
     return (delta_w < rrects[None, :, 2] / 2) & (delta_h < rrects[None, :, 3] / 2)
+
+
+def mintheta_obb(obboxes):
+    """(…, 5) boxes with the side order swapped where that brings the angle nearer 0: of theta and theta + pi/2, both
+    folded into [-pi/2, pi/2), the one of smaller magnitude (box_ops.py:L679-692; `pi = 3.141592` is the reference's)."""
+    from jdet_amd.ops.bbox_transforms import regular_theta
+    pi = 3.141592
+    x, y, w, h, theta = obboxes.unbind(dim=-1)
+    theta1 = regular_theta(theta)
+    theta2 = regular_theta(theta + pi / 2)
+    first = torch.abs(theta1) < torch.abs(theta2)
+    w_regular = torch.where(first, w, h)
+    h_regular = torch.where(first, h, w)
+    theta_regular = torch.where(first, theta1, theta2)
+    return torch.stack([x, y, w_regular, h_regular, theta_regular], dim=-1)
+
+
+def distance2obb(points, distance, max_shape=None):
+    """(n, 2) points + (n, 5) [l, t, r, b, theta] -> (n, 5) regular_obb boxes (box_ops.py:L694-707; `max_shape` is
+    accepted and unused, as there).  The inverse of the FCOS point targets: centre = point + R(theta)^T-rotated half
+    difference of the distances, size = their sums."""
+    from jdet_amd.ops.bbox_transforms import regular_obb
+    distance, theta = distance.split([4, 1], dim=1)
+    Cos, Sin = torch.cos(theta), torch.sin(theta)
+    Matrix = torch.cat([Cos, Sin, -Sin, Cos], dim=1).reshape(-1, 2, 2)
+    wh = distance[:, :2] + distance[:, 2:]
+    offset_t = ((distance[:, 2:] - distance[:, :2]) / 2).unsqueeze(2)
+    offset = torch.bmm(Matrix, offset_t).squeeze(2)
+    ctr = points + offset
+    return regular_obb(torch.cat([ctr, wh, theta], dim=1))

@@ -3,3 +3,4 @@ from .s2anet import S2ANet  # noqa: F401
 from .rotated_retinanet import RotatedRetinaNet  # noqa: F401
 from .roi_transformer import RoITransformer  # noqa: F401
 from .gliding_vertex import GlidingVertex  # noqa: F401
+from .fcos import FCOS, SingleStageDetector  # noqa: F401

@@ -9,3 +9,4 @@ from .convfc_rbbox_head import ConvFCBBoxHeadRbbox, SharedFCBBoxHeadRbbox  # noq
 from .fasterrcnn_head import AnchorHead, FasterrcnnHead  # noqa: F401
 from .gliding_rpn_head import GlidingRPNHead  # noqa: F401
 from .gliding_head import GlidingHead  # noqa: F401
+from .fcos_head import FCOSHead  # noqa: F401
