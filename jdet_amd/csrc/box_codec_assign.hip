@@ -238,6 +238,7 @@ __global__ __launch_bounds__(256) void obb2hbb2obb_kernel(const float* __restric
   o[4] = flag ? 0.f : 0.f - (float)(M_PI / 2);
 }
 
+// the cap: tests/test_gpu_codecs.py reads it off this line and launches just past 262144 x 256 elements
 inline int grid_for(long n) {
   long g = (n + 255) / 256;
   return (int)(g > 262144 ? 262144 : (g < 1 ? 1 : g));

@@ -172,6 +172,7 @@ __global__ __launch_bounds__(256) void oriented_encode_kernel(const float* __res
   }
 }
 
+// the cap: tests/test_gpu_codecs.py reads it off this line and launches just past 65536 x 256 elements
 inline int grid_for(long n) {
   long g = (n + 255) / 256;
   return (int)(g > 65536 ? 65536 : (g < 1 ? 1 : g));

@@ -2,9 +2,9 @@
 norm_angle L176-178, bbox2delta_rotated L180-226, delta2bbox_rotated L229-285,
 rotated_box_to_poly L592-613, points_in_rotated_boxes L725-741.
 
-On a HIP device and outside autograd the two coders run as ONE fused kernel each
-(csrc/box_codec_assign.hip); the torch expressions below are the differentiable form (needed when
-a loss is applied to decoded boxes) and define the same arithmetic.
+On a HIP device and outside autograd the two coders run as ONE fused fp32 kernel each
+(csrc/box_codec_assign.hip; half inputs are up-cast); the torch expressions below are the differentiable form
+(needed when a loss is applied to decoded boxes), define the same arithmetic and serve float64 inputs in float64.
 """
 import math
 
@@ -23,6 +23,13 @@ def _fused_ok(*ts):
     return all(t.is_cuda for t in ts) and not (torch.is_grad_enabled() and any(t.requires_grad for t in ts))
 
 
+def _fused_no64_ok(*ts):
+    """`_fused_ok` unless an input is float64: the kernels are fp32, and a float64 caller is promised the float64
+    composition below, not a silent down-cast.  Half and bfloat16 inputs (a head under autocast) are up-cast to the
+    one fp32 launch, as before"""
+    return _fused_ok(*ts) and not any(t.dtype == torch.float64 for t in ts)
+
+
 def _vec5(v):
     import ctypes
     return (ctypes.c_float * 5)(*[float(x) for x in v])
@@ -30,7 +37,7 @@ def _vec5(v):
 
 def bbox2delta_rotated(proposals, gt, means=(0., 0., 0., 0., 0.), stds=(1., 1., 1., 1., 1.)):
     assert proposals.size() == gt.size()
-    if _fused_ok(proposals, gt) and proposals.dim() == 2:
+    if _fused_no64_ok(proposals, gt) and proposals.dim() == 2:
         p, g = L.f32c(proposals), L.f32c(gt)
         out = torch.empty_like(p)
         L.check(L.lib().jdet_bbox2delta_rotated(L.ptr(p), L.ptr(g), p.shape[0], _vec5(means), _vec5(stds),
@@ -55,7 +62,7 @@ def delta2bbox_rotated(rois, deltas, means=(0., 0., 0., 0., 0.), stds=(1., 1., 1
                        wh_ratio_clip=16 / 1000, clip_border=True):
     """rois (N,5), deltas (N, 5*num_classes) -> (N, 5*num_classes).  `max_shape` / `clip_border` are
     accepted but never applied, exactly as in the reference (box_ops.py:L229-285)."""
-    if _fused_ok(rois, deltas) and deltas.dim() == 2 and deltas.shape[1] % 5 == 0:
+    if _fused_no64_ok(rois, deltas) and deltas.dim() == 2 and deltas.shape[1] % 5 == 0:
         r, d = L.f32c(rois), L.f32c(deltas)
         out = torch.empty_like(d)
         L.check(L.lib().jdet_delta2bbox_rotated(L.ptr(r), L.ptr(d), d.shape[0], d.shape[1] // 5, _vec5(means),

@@ -19,6 +19,24 @@ def _fused_ok(*ts):
                                                                   any(t.requires_grad for t in ts))
 
 
+def _fused32_ok(*ts):
+    """`_fused_ok` for float32 inputs only: the kernels are fp32, and a float64 caller is promised the float64
+    composition, not a silent down-cast"""
+    return _fused_ok(*ts) and all(t.dtype == torch.float32 for t in ts)
+
+
+def _fused_no64_ok(*ts):
+    """`_fused_ok` unless an input is float64 (the Oriented R-CNN coders): the kernels are fp32, and a float64 caller is
+    promised the float64 composition, not a silent down-cast.  Half and bfloat16 inputs (a head under autocast) are
+    up-cast to the one fp32 launch, as before"""
+    return _fused_ok(*ts) and not any(t.dtype == torch.float64 for t in ts)
+
+
+def _floating(t):
+    """the reference's `.float()`, except that float64 stays float64"""
+    return t if t.dtype == torch.float64 else t.float()
+
+
 @BOXES.register_module()
 class DeltaXYWHABBoxCoder:
     """encodes (x,y,w,h,a) into (dx,dy,dw,dh,da) relative to a base box and back."""
@@ -50,14 +68,14 @@ class MidpointOffsetCoder:
 
     def encode(self, bboxes, gt_bboxes):
         assert bboxes.size(0) == gt_bboxes.size(0)
-        if _fused_ok(bboxes, gt_bboxes) and bboxes.shape[1] == 4 and gt_bboxes.shape[1] == 5:
+        if _fused_no64_ok(bboxes, gt_bboxes) and bboxes.shape[1] == 4 and gt_bboxes.shape[1] == 5:
             a, g = L.f32c(bboxes), L.f32c(gt_bboxes)
             out = torch.empty((a.shape[0], 6), dtype=torch.float32, device=a.device)
             L.check(L.lib().jdet_midpoint_offset_encode(L.ptr(a), L.ptr(g), a.shape[0], L.vecn(self.means, 6),
                                                         L.vecn(self.stds, 6), L.ptr(out), L.stream_ptr(a)),
                     "jdet_midpoint_offset_encode")
             return out
-        pred_bboxes, gt = bboxes.float(), gt_bboxes.float()
+        pred_bboxes, gt = _floating(bboxes), _floating(gt_bboxes)
         px = (pred_bboxes[..., 0] + pred_bboxes[..., 2]) * 0.5
         py = (pred_bboxes[..., 1] + pred_bboxes[..., 3]) * 0.5
         pw = pred_bboxes[..., 2] - pred_bboxes[..., 0]
@@ -89,7 +107,7 @@ class MidpointOffsetCoder:
 
     def decode(self, bboxes, pred_bboxes, max_shape=None, wh_ratio_clip=16 / 1000):
         assert pred_bboxes.size(0) == bboxes.size(0)
-        if _fused_ok(bboxes, pred_bboxes) and bboxes.shape[1] == 4 and pred_bboxes.shape[1] == 6:
+        if _fused_no64_ok(bboxes, pred_bboxes) and bboxes.shape[1] == 4 and pred_bboxes.shape[1] == 6:
             a, d = L.f32c(bboxes), L.f32c(pred_bboxes)
             out = torch.empty((a.shape[0], 5), dtype=torch.float32, device=a.device)
             L.check(L.lib().jdet_midpoint_offset_decode(L.ptr(a), L.ptr(d), a.shape[0], L.vecn(self.means, 6),
@@ -137,15 +155,15 @@ class OrientedDeltaXYWHTCoder:
     def encode(self, bboxes, gt_bboxes):
         assert bboxes.size(0) == gt_bboxes.size(0)
         assert bboxes.size(-1) == gt_bboxes.size(-1) == 5
-        if _fused_ok(bboxes, gt_bboxes):
+        if _fused_no64_ok(bboxes, gt_bboxes):
             p, g = L.f32c(bboxes), L.f32c(gt_bboxes)
             out = torch.empty_like(p)
             L.check(L.lib().jdet_oriented_delta_encode(L.ptr(p), L.ptr(g), p.shape[0], L.vecn(self.means, 5),
                                                        L.vecn(self.stds, 5), L.ptr(out), L.stream_ptr(p)),
                     "jdet_oriented_delta_encode")
             return out
-        px, py, pw, ph, ptheta = bboxes.float().unbind(dim=-1)
-        gx, gy, gw, gh, gtheta = gt_bboxes.float().unbind(dim=-1)
+        px, py, pw, ph, ptheta = _floating(bboxes).unbind(dim=-1)
+        gx, gy, gw, gh, gtheta = _floating(gt_bboxes).unbind(dim=-1)
         dtheta1 = regular_theta(gtheta - ptheta)
         dtheta2 = regular_theta(gtheta - ptheta + math.pi / 2)
         m = (torch.abs(dtheta1) < torch.abs(dtheta2)).to(px.dtype)
@@ -163,7 +181,7 @@ class OrientedDeltaXYWHTCoder:
 
     def decode(self, bboxes, pred_bboxes, max_shape=None, wh_ratio_clip=16 / 1000):
         assert pred_bboxes.size(0) == bboxes.size(0)
-        if _fused_ok(bboxes, pred_bboxes) and bboxes.shape[1] == 5 and pred_bboxes.shape[1] % 5 == 0:
+        if _fused_no64_ok(bboxes, pred_bboxes) and bboxes.shape[1] == 5 and pred_bboxes.shape[1] % 5 == 0:
             r, d = L.f32c(bboxes), L.f32c(pred_bboxes)
             out = torch.empty_like(d)
             L.check(L.lib().jdet_oriented_delta_decode(L.ptr(r), L.ptr(d), d.shape[0], d.shape[1] // 5,
@@ -195,12 +213,6 @@ class OrientedDeltaXYWHTCoder:
 # the torch compositions below are what runs on the host, in float64 and wherever a gradient is asked for.  The Jittor
 # programs themselves cannot be run here (Jittor is not importable): the compositions are pinned by the restatement in
 # tests/gliding_ref.py and its closed forms only.
-
-def _fused32_ok(*ts):
-    """`_fused_ok` for float32 inputs only: the kernels are fp32, and a float64 caller is promised the float64
-    composition, not a silent down-cast"""
-    return _fused_ok(*ts) and all(t.dtype == torch.float32 for t in ts)
-
 
 def _max_hw(max_shape):
     """(h, w) of a `max_shape` argument as floats; (0, 0) = no clamp"""

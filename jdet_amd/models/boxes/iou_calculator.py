@@ -40,11 +40,11 @@ class BboxOverlaps2D_rotated_v1(_RotatedOverlaps):
 
 def fake_rotated_boxes(boxes):
     """hbb2obb(obb2hbb(boxes)) (ops/bbox_transforms.py:L639-665 of the reference): the enclosing horizontal box as an
-    OBB.  Device tensors: ONE launch (jdet_obb2hbb2obb), the same operations in the same order as the tensor program;
-    host tensors: that program."""
+    OBB.  Device tensors: ONE fp32 launch (jdet_obb2hbb2obb), the same operations in the same order as the tensor
+    program; host tensors and float64 device tensors (no silent down-cast): that program."""
     import torch
     from jdet_amd import _lib as L
-    if not boxes.is_cuda:
+    if not boxes.is_cuda or boxes.dtype == torch.float64:
         from jdet_amd.ops.bbox_transforms import hbb2obb, obb2hbb
         return hbb2obb(obb2hbb(boxes))
     b = L.f32c(boxes)

@@ -1450,6 +1450,43 @@ row("jdet_oriented_delta_decode", "n 257 ncls 3")(_oriented("ori_decode"))
 row("jdet_oriented_delta_encode", "n 257")(_oriented("ori_encode"))
 
 
+def _codec64(name):
+    """what the rows above leave out -- 15 classes on 257 rois (no multiple of 15) and wh_ratio_clip 0.25 -- on the first
+    257 rows of a fixture of tests/codec_ref.py: the float64 restatement, the error measures and the bound (4 x the
+    float32 restatement's own error on the fixture) of tests/test_gpu_codecs.py; elements the fixture's retention
+    margins keep out are not compared"""
+    def fn(run):
+        from tests import codec_ref as CR
+        f = CR.fixture(name)
+        n, C = ORI_N, f.ncls
+        a0, d0 = (np.array(a[:n]) for a in f.args)                    # writable copies of the read-only fixture
+        a, d, out = run.inp("boxes", a0), run.inp("deltas", d0), run.out("out", (n, 5 * C))
+        m, s, clip = f.kw["means"], f.kw["stds"], f.kw["wh_ratio_clip"]
+        assert clip == 0.25
+        if f.codec == "d2b":
+            rc = lib().jdet_delta2bbox_rotated(P(a), P(d), n, C, c5(m), c5(s), clip, P(out), ST(d))
+        elif f.codec == "ori_dec":
+            rc = lib().jdet_oriented_delta_decode(P(a), P(d), n, C, c5(m), c5(s), clip, P(out), ST(d))
+        else:
+            rc = lib().jdet_midpoint_offset_decode(P(a), P(d), n, L.vecn(m, 6), L.vecn(s, 6), clip, P(out), ST(d))
+        run.ok(rc, CR.ENTRY_POINT[f.codec])
+
+        def ref():
+            keep, b = f.keep[:n], f.bound()
+
+            def err(v):
+                e = CR.errors(f.codec, np.asarray(v, np.float64).reshape(n, -1), f.ref[:n])
+                return np.stack([np.where(keep, e["xywh"], 0.0), np.where(keep, e["angle"], 0.0)], -1)
+            return {"out": (err, np.broadcast_to(np.asarray([b["xywh"], b["angle"]]), (n, C, 2)).reshape(-1).copy())}
+        return Res({"out": out}, ref)
+    return fn
+
+
+row("jdet_delta2bbox_rotated", "n 257 ncls 15 wh_ratio_clip 0.25, float64 reference")(_codec64("d2b_lo15"))
+row("jdet_oriented_delta_decode", "n 257 ncls 15 wh_ratio_clip 0.25, float64 reference")(_codec64("ori_dec_lo15"))
+row("jdet_midpoint_offset_decode", "n 257 wh_ratio_clip 0.25, float64 reference")(_codec64("mid_dec_lo"))
+
+
 def gv_bound(f32, f64):
     """tests/test_gpu_gliding.py:25-26: 4 x the largest float32-vs-float64 difference of the restatement, floor 1e-6"""
     return np.asarray(f64, np.float64), max(4.0 * float(np.abs(np.asarray(f32).astype(np.float64) - f64).max()), 1e-6)
