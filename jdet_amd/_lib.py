@@ -166,6 +166,15 @@ ROWS_SIGNATURES = {
     "jdet_conv3x3_dgrad_rows": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p]),
 }
 
+# include/jdet_hip_rows_fwd.h (csrc/conv_rows.hip; same library, a table of its own because tests/test_conv_rows_cpu.py pins
+# the names of ROWS_SIGNATURES; tests/test_conv_rows_fwd_cpu.py checks it against the header and the exports)
+ROWS_FWD_SIGNATURES = {
+    "jdet_rows_from_flags_workspace": (_sz, [_i, _i, _i]),
+    "jdet_rows_from_flags": (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _p, _sz, _p]),
+    "jdet_conv3x3_rows_forward_supported": (_i, [_i, _i]),
+    "jdet_conv3x3_rows_forward": (_i, [_p, _p, _p, _i, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p]),
+}
+
 # include/jdet_hip_fcos.h (csrc/fcos_targets.hip, csrc/poly_iou_loss.hip; same library, a table of its own for the reason
 # ATSS_SIGNATURES has one; tests/test_fcos_cpu.py checks it against the header and the exports)
 FCOS_SIGNATURES = {
@@ -204,7 +213,7 @@ def lib():
         # streams and allocations.
         l = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in list(SIGNATURES.items()) + list(ATSS_SIGNATURES.items()) + list(ROWS_SIGNATURES.items()) + \
-                list(FCOS_SIGNATURES.items()):
+                list(ROWS_FWD_SIGNATURES.items()) + list(FCOS_SIGNATURES.items()):
             fn = getattr(l, name)  # AttributeError here == ABI drift: fail loudly
             fn.restype = res
             fn.argtypes = args

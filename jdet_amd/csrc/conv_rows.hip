@@ -18,12 +18,21 @@
 //                            tile taken from the list and an epilogue that scatters rows; Wd = the flipped weights of
 //                            jdet_conv_dgrad_weights
 //
+// and, for the FORWARD of a tower whose output only that loss reads (include/jdet_hip_rows_fwd.h; in training the ODM
+// regression tower, whose prediction bbox_decode / AlignConv do not read):
+//
+//   jdet_rows_from_flags       a flag byte per position -> the ascending lists of the flagged rows, of their 3x3 dilation
+//                              and of the dilation of that, with their counts (the dilation / list launches above, twice)
+//   jdet_conv3x3_rows_forward  y[r] = [relu](sum_tap x[nbr(r, tap)] . w[tap] + bias) * rowmask[r] for r in a list
+//                              = the data gradient's tile with conv_igemm.hip's epilogue, on the (Cout, 3, 3, Cin) weights
+//
 // Nothing is read back to the host and no launch shape depends on device data: the grids are fixed by CAPACITY (all P
 // rows), the counts are read by the kernels, and workgroups past a count leave at once.  A fully dense gradient is
 // computed correctly, only slower than by the dense kernels.  List entries past a count are -1 and never read.
 // Results equal the dense computation with the exact zeros left out of the sums.
 #include "conv_mfma.h"
 #include "jdet_hip_rows.h"
+#include "jdet_hip_rows_fwd.h"
 
 namespace {
 
@@ -326,6 +335,11 @@ void conv3x3_wgrad_rows_kernel(WgradRowsArgs a) {
 // =====================================================================================================================
 // jdet_conv3x3_dgrad_rows: conv_igemm.hip's 64 x 64 tile.  "Input" = g with KC = Cout channels, "weights" = Wd
 // (Cin, 3, 3, Cout), outputs = NO = Cin channels of gx.  M tile t holds the list entries [64 t, 64 t + 64).
+//
+// jdet_conv3x3_rows_forward (FWD) is the same tile read the other way round: out[r] = sum_tap in[nbr(r, tap)] . w[tap] is
+// a forward convolution whose (NO, 3, 3, KC) weights are the (Cout, 3, 3, Cin) layout of the dense forward -- "input" = x
+// (the `Cout` field holds ITS channel count), outputs = the `Cin` field's channels of y -- and whose epilogue is
+// conv_igemm.hip's: + bias, ReLU, times the row's mask.  One body; the epilogue is selected at compile time.
 struct DgradRowsArgs {
   const float* g;        // (N, H, W, Cout)
   const float* wd;       // (Cin, 3, 3, Cout): flipped taps (jdet_conv_dgrad_weights)
@@ -333,9 +347,12 @@ struct DgradRowsArgs {
   const int* count;
   float* gx;             // (N, H, W, Cin); only the listed rows are written
   int N, H, W, Cin, Cout;
+  const float* bias;     // FWD only: (Cin field) or null
+  const float* rowmask;  // FWD only: (N*H*W) or null, multiplies the finished row (after bias / ReLU)
+  int relu;              // FWD only
 };
 
-template <int BK, int KG>
+template <int BK, int KG, bool FWD>
 __global__ __launch_bounds__(256 * KG) __attribute__((amdgpu_waves_per_eu(4)))
 void conv3x3_dgrad_rows_kernel(DgradRowsArgs a) {
   constexpr int BT = 64;
@@ -457,16 +474,25 @@ void conv3x3_dgrad_rows_kernel(DgradRowsArgs a) {
   const int lrow0 = m0 + wm * (BT / 2) + 4 * (lane >> 5);
   const int n = n0 + wn * (BT / 2) + (lane & 31);
   unsigned dst[16];
+  float mk[16];
+  float b = 0.f;
+  if constexpr (FWD) b = (a.bias && n < NO) ? a.bias[n] : 0.f;
 #pragma unroll
   for (int e = 0; e < 16; e++) {
     const int li = lrow0 + cd_row(e);
     const unsigned pos = li < cnt ? (unsigned)a.rows[li] : 0xFFFFFFFFu;
     dst[e] = (pos < (unsigned)P && n < NO) ? (pos * (unsigned)NO + (unsigned)n) * 4u : kOob;
+    if constexpr (FWD) mk[e] = (a.rowmask && pos < (unsigned)P) ? a.rowmask[pos] : 1.f;      // all 16 loads in flight together
   }
 #pragma unroll
   for (int e = 0; e < 16; e++) {
     float v = acc[0][0][e];
     if (KG == 2) v += reinterpret_cast<const float*>(s_raw)[red_index<T>(wave, lane, 0, 0, e)];
+    if constexpr (FWD) {      // conv_igemm.hip's epilogue, in its order
+      v += b;
+      if (a.relu) v = fmaxf(v, 0.f);
+      if (a.rowmask) v *= mk[e];
+    }
     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), ry, dst[e], 0u, 0);
   }
 }
@@ -557,9 +583,74 @@ JDET_API int jdet_conv3x3_dgrad_rows(const float* gy_nhwc, const float* wd_crsk,
     const int e = jdet_zero_async(gx_nhwc, sizeof(float) * (size_t)P * Cin, st);
     if (e) return e;
   }
-  DgradRowsArgs a{gy_nhwc, wd_crsk, rows, count, gx_nhwc, N, H, W, Cin, Cout};
+  DgradRowsArgs a{gy_nhwc, wd_crsk, rows, count, gx_nhwc, N, H, W, Cin, Cout, nullptr, nullptr, 0};
   const unsigned grid = (unsigned)(((P + 63) / 64) * ((Cin + 63) / 64));
-  if (Cout % 32 == 0) hipLaunchKernelGGL((conv3x3_dgrad_rows_kernel<32, 2>), dim3(grid), dim3(512), 0, st, a);
-  else hipLaunchKernelGGL((conv3x3_dgrad_rows_kernel<16, 1>), dim3(grid), dim3(256), 0, st, a);
+  if (Cout % 32 == 0) hipLaunchKernelGGL((conv3x3_dgrad_rows_kernel<32, 2, false>), dim3(grid), dim3(512), 0, st, a);
+  else hipLaunchKernelGGL((conv3x3_dgrad_rows_kernel<16, 1, false>), dim3(grid), dim3(256), 0, st, a);
+  return jdet_launch_status();
+}
+
+// =====================================================================================================================
+// include/jdet_hip_rows_fwd.h
+
+JDET_API size_t jdet_rows_from_flags_workspace(int N, int H, int W) {
+  if (N <= 0 || H <= 0 || W <= 0) return 0;
+  const long P = (long)N * H * W;
+  const long nb = (P + kBlk - 1) / kBlk;
+  return 2 * align16((size_t)P) + sizeof(int32_t) * 4 * (size_t)nb;
+}
+
+JDET_API int jdet_rows_from_flags(const uint8_t* flags, int N, int H, int W, int32_t* rows, int32_t* rows_dilated,
+                                  int32_t* rows_dilated2, int32_t* counts, void* workspace, size_t workspace_bytes,
+                                  jdet_stream_t stream) {
+  if (N <= 0 || H <= 0 || W <= 0) return JDET_E_BADARG;
+  const long P = (long)N * H * W;
+  if (P >= (1L << 30)) return JDET_E_UNSUPPORTED;                     // positions are int32 list entries
+  if (!flags || !rows || !rows_dilated || !rows_dilated2 || !counts) return JDET_E_BADARG;
+  if (((uintptr_t)rows | (uintptr_t)rows_dilated | (uintptr_t)rows_dilated2 | (uintptr_t)counts) & 3) return JDET_E_BADARG;
+  if (!workspace || workspace_bytes < jdet_rows_from_flags_workspace(N, H, W)) return JDET_E_WORKSPACE;
+  if ((uintptr_t)workspace & 3) return JDET_E_BADARG;
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned nb = (unsigned)((P + kBlk - 1) / kBlk);
+  uint8_t* d1 = (uint8_t*)workspace;
+  uint8_t* d2 = d1 + align16((size_t)P);
+  int* c0 = (int*)(d2 + align16((size_t)P));
+  int* c1 = c0 + nb;
+  int* c1b = c1 + nb;       // the count of d1 once more (the second dilation's "flag" count)
+  int* c2 = c1b + nb;
+  hipLaunchKernelGGL(rows_dilate_kernel, dim3(nb), dim3(256), 0, st, flags, H, W, P, d1, c0, c1);
+  hipLaunchKernelGGL(rows_dilate_kernel, dim3(nb), dim3(256), 0, st, (const uint8_t*)d1, H, W, P, d2, c1b, c2);
+  hipLaunchKernelGGL(rows_list_kernel, dim3(nb), dim3(256), 0, st, flags, (const uint8_t*)d1, P, (const int*)c0,
+                     (const int*)c1, rows, rows_dilated, counts);
+  // (writes rows_dilated and counts[1] a second time, with the same values: the kernels stay the two of jdet_rows_nonzero)
+  hipLaunchKernelGGL(rows_list_kernel, dim3(nb), dim3(256), 0, st, (const uint8_t*)d1, (const uint8_t*)d2, P,
+                     (const int*)c1b, (const int*)c2, rows_dilated, rows_dilated2, counts + 1);
+  return jdet_launch_status();
+}
+
+JDET_API int jdet_conv3x3_rows_forward_supported(int Cin, int Cout) {
+  return Cin > 0 && Cout > 0 && Cin % 16 == 0 && Cout % 16 == 0;
+}
+
+JDET_API int jdet_conv3x3_rows_forward(const float* x_nhwc, const float* w_krsc, const float* bias, int relu,
+                                       const float* rowmask, const int32_t* rows, const int32_t* count, int N, int H,
+                                       int W, int Cin, int Cout, int zero_first, float* y_nhwc, jdet_stream_t stream) {
+  if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return JDET_E_BADARG;
+  if (!jdet_conv3x3_rows_forward_supported(Cin, Cout)) return JDET_E_UNSUPPORTED;
+  const long P = (long)N * H * W;
+  if (P * (Cin > Cout ? Cin : Cout) >= (1L << 30)) return JDET_E_UNSUPPORTED;               // 32-bit byte offsets
+  if (!x_nhwc || !w_krsc || !rows || !count || !y_nhwc) return JDET_E_BADARG;
+  if ((((uintptr_t)x_nhwc) | ((uintptr_t)w_krsc)) & 15) return JDET_E_BADARG;
+  if (((uintptr_t)rows | (uintptr_t)count | (uintptr_t)y_nhwc | (uintptr_t)bias | (uintptr_t)rowmask) & 3) return JDET_E_BADARG;
+  hipStream_t st = (hipStream_t)stream;
+  if (zero_first) {
+    const int e = jdet_zero_async(y_nhwc, sizeof(float) * (size_t)P * Cout, st);
+    if (e) return e;
+  }
+  // the tile's "Cin" field = its output channels, its "Cout" field = the K channels (see DgradRowsArgs)
+  DgradRowsArgs a{x_nhwc, w_krsc, rows, count, y_nhwc, N, H, W, Cout, Cin, bias, rowmask, relu ? 1 : 0};
+  const unsigned grid = (unsigned)(((P + 63) / 64) * ((Cout + 63) / 64));
+  if (Cin % 32 == 0) hipLaunchKernelGGL((conv3x3_dgrad_rows_kernel<32, 2, true>), dim3(grid), dim3(512), 0, st, a);
+  else hipLaunchKernelGGL((conv3x3_dgrad_rows_kernel<16, 1, true>), dim3(grid), dim3(256), 0, st, a);
   return jdet_launch_status();
 }

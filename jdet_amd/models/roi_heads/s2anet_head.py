@@ -189,12 +189,17 @@ class S2ANetHead(RotatedAnchorHeadMixin, nn.Module):
         refine_anchor = bbox_decode(fam_bbox_pred.detach(), init_anchors, self.target_means, self.target_stds)
         return refine_anchor, self.align_conv(x, refine_anchor, stride)     # (read-only there: no copy needed)
 
-    def _odm(self, align_feat, mask=None, rows=None):
+    def _odm_front(self, align_feat, mask=None, rows=None):
+        """everything of the ODM but its regression branch: (or_feat, odm_cls_score)"""
         or_feat = self.or_conv(align_feat)
         if mask is not None:
             or_feat = or_feat * mask
         odm_cls_feat = self.or_pool(or_feat) if self.with_orconv else or_feat
         odm_cls_score = conv_module(self.odm_cls, self._towers(odm_cls_feat, self.odm_cls_convs, mask, rows))
+        return or_feat, odm_cls_score
+
+    def _odm(self, align_feat, mask=None, rows=None):
+        or_feat, odm_cls_score = self._odm_front(align_feat, mask, rows)
         odm_bbox_pred = conv_module(self.odm_reg, self._towers(or_feat, self.odm_reg_convs, mask, rows))
         return odm_cls_score, odm_bbox_pred
 
@@ -232,8 +237,19 @@ class S2ANetHead(RotatedAnchorHeadMixin, nn.Module):
         return refine_anchors_list, valid_flag_list
 
     # ------------------------------------------------------------------ loss
+    def _odm_targets(self, featmap_sizes, refine_anchors, gt_bboxes, gt_labels, img_metas, gt_bboxes_ignore, device):
+        """the ODM `anchor_target` on the refined anchors of ALL levels (the assigner works over an image's levels)"""
+        refine_anchors_list, valid_flag_list = self.get_refine_anchors(featmap_sizes, refine_anchors, img_metas,
+                                                                       device=device)
+        label_channels = self.cls_out_channels if self.use_sigmoid_cls else 1
+        return anchor_target(refine_anchors_list, valid_flag_list, gt_bboxes, img_metas, self.target_means,
+                             self.target_stds, self.train_cfg.odm_cfg, gt_bboxes_ignore_list=gt_bboxes_ignore,
+                             gt_labels_list=gt_labels, label_channels=label_channels, sampling=self.sampling)
+
     def loss(self, fam_cls_scores, fam_bbox_preds, refine_anchors, odm_cls_scores, odm_bbox_preds, gt_bboxes,
-             gt_labels, img_metas, gt_bboxes_ignore=None):
+             gt_labels, img_metas, gt_bboxes_ignore=None, odm_targets=None):
+        """odm_targets: what `_odm_targets` returned for these refined anchors (the training forward computes them
+        before the ODM regression tower runs: `_forward_train_rows`), else they are computed here"""
         cfg = self.train_cfg.copy()
         featmap_sizes = [tuple(featmap.shape[-2:]) for featmap in odm_cls_scores]
         assert len(featmap_sizes) == len(self.anchor_generators)
@@ -268,10 +284,12 @@ class S2ANetHead(RotatedAnchorHeadMixin, nn.Module):
         if need_anchors:
             concat_anchor_list = [torch.cat(refine_anchors_list[i]) for i in range(len(refine_anchors_list))]
             all_anchor_list = images_to_levels(concat_anchor_list, num_level_anchors)
-        cls_reg_targets = anchor_target(refine_anchors_list, valid_flag_list, gt_bboxes, img_metas, self.target_means,
-                                        self.target_stds, cfg.odm_cfg, gt_bboxes_ignore_list=gt_bboxes_ignore,
-                                        gt_labels_list=gt_labels, label_channels=label_channels,
-                                        sampling=self.sampling)
+        cls_reg_targets = odm_targets
+        if cls_reg_targets is None:
+            cls_reg_targets = anchor_target(refine_anchors_list, valid_flag_list, gt_bboxes, img_metas,
+                                            self.target_means, self.target_stds, cfg.odm_cfg,
+                                            gt_bboxes_ignore_list=gt_bboxes_ignore, gt_labels_list=gt_labels,
+                                            label_channels=label_channels, sampling=self.sampling)
         if cls_reg_targets is None:
             return None
         (labels_list, label_weights_list, bbox_targets_list, bbox_weights_list, num_total_pos, num_total_neg) = \
@@ -354,7 +372,91 @@ class S2ANetHead(RotatedAnchorHeadMixin, nn.Module):
                         t.record_stream(main)
         return tuple(map(list, zip(*outs)))
 
+    # ------------------------------------------------------------------ training forward, ODM regression tower on rows
+    def _rows_forward_route(self, feats):
+        """In training `odm_bbox_pred` is read by the smooth-L1 loss only, which weighs every anchor that is not positive
+        with 0 (bbox_decode / AlignConv read fam_bbox_pred, get_bboxes runs in eval mode): the two odm_reg_convs layers
+        are needed only where they feed a positive anchor.  True where `_forward_train_rows` applies: plain conv + bias
+        + ReLU tower layers on the fused fp32 path, the rows switches on (ops/conv_igemm: ROWS, ROWS_FWD)."""
+        from jdet_amd.ops import conv_igemm as CI
+        if not (self.training and torch.is_grad_enabled() and not HEAD_STREAMS and len(feats) > 0):
+            return False
+        for m in self.odm_reg_convs:
+            if (not isinstance(m, ConvModule) or m.with_norm or not m.with_activation or type(m.activate) is not nn.ReLU
+                    or m.order.index("conv") > m.order.index("act") or not m.row_sparse_grad):
+                return False
+        if type(self.odm_reg) is not nn.Conv2d or self.odm_reg.kernel_size != (3, 3) or self.odm_reg.padding != (1, 1):
+            return False            # (the dilation count below is that of a 3x3 prediction layer)
+        convs = [m.conv for m in self.odm_reg_convs]
+        if not all(f.dim() == 4 and CI.rows_tower_applicable(convs, f) for f in feats):
+            return False
+        small = [f for f in feats if f.shape[-2] * f.shape[-1] <= self.pack_max_positions]
+        if len(small) >= 2:        # the packed levels run as one canvas
+            pack = LevelPack.cached([tuple(f.shape[-2:]) for f in small], small[0].device)
+            return CI.rows_tower_applicable(convs, small[0], small[0].shape[0] * pack.height * pack.width)
+        return True
+
+    def _forward_train_rows(self, feats, targets):
+        """`loss(*_level_outputs(feats))` with the ODM regression tower computed on the rows its loss reads:
+        1. FAM, refine, AlignConv, or_conv and the ODM classification branch for ALL levels (packed and per level),
+        2. the ODM targets on the refined anchors (the loss reuses them),
+        3. a flag byte per position (per canvas position for the pack) from the targets' bbox_weights,
+        4. odm_reg_convs through ops/conv_igemm.rows_tower into zero-filled maps, 5. odm_reg dense.
+        No host synchronisation and no launch shape from device data."""
+        from jdet_amd.ops import conv_igemm as CI
+        gt_bboxes, gt_labels, img_metas, gt_bboxes_ignore = self.parse_targets(targets)
+        n = len(feats)
+        fam_cls, fam_box, refine, odm_cls, odm_box = ([None] * n for _ in range(5))
+        small = [i for i, f in enumerate(feats)
+                 if f.is_cuda and f.shape[-2] * f.shape[-1] <= self.pack_max_positions]
+        groups = []                # (levels, their pack or None, or_feat)
+        if len(small) >= 2:
+            xs = [feats[i] for i in small]
+            pack = LevelPack.cached([tuple(x.shape[-2:]) for x in xs], xs[0].device)
+            mask = pack.mask.to(xs[0].dtype)
+            rows = pack.row_mask(xs[0].shape[0]) if FUSED_PACK_MASK and xs[0].dtype == torch.float32 else None
+            fam_cls_p, fam_box_p = self._fam(pack.pack(xs), mask, rows)
+            boxes, scores = pack.unpack(fam_box_p), pack.unpack(fam_cls_p)
+            refined = [self._refine(x, b, self.anchor_strides[i]) for x, b, i in zip(xs, boxes, small)]
+            or_feat, odm_cls_p = self._odm_front(pack.pack([r[1] for r in refined]), mask, rows)
+            for k, (i, c) in enumerate(zip(small, pack.unpack(odm_cls_p))):
+                fam_cls[i], fam_box[i], refine[i], odm_cls[i] = scores[k], boxes[k], refined[k][0], c
+            groups.append((small, pack, or_feat))
+        else:
+            small = []
+        for i, f in enumerate(feats):
+            if i in small:
+                continue
+            fam_cls[i], fam_box[i] = self._fam(f)
+            refine[i], align_feat = self._refine(f, fam_box[i], self.anchor_strides[i])
+            or_feat, odm_cls[i] = self._odm_front(align_feat)
+            groups.append(([i], None, or_feat))
+
+        featmap_sizes = [tuple(f.shape[-2:]) for f in feats]
+        odm_targets = self._odm_targets(featmap_sizes, refine, gt_bboxes, gt_labels, img_metas, gt_bboxes_ignore,
+                                        feats[0].device)
+        if odm_targets is None:
+            return None            # (what loss() returns for it)
+        num_imgs = feats[0].shape[0]
+        with torch.no_grad():      # bbox_weights (n, anchors of the level, 5): a position is listed if any weight is set
+            flags = [bw.reshape(num_imgs, h * w, -1).ne(0).any(-1) for bw, (h, w) in zip(odm_targets[3], featmap_sizes)]
+        convs = [m.conv for m in self.odm_reg_convs]
+        for levels, pack, or_feat in groups:
+            if pack is None:
+                odm_box[levels[0]] = conv_module(self.odm_reg, CI.rows_tower(convs, or_feat, flags[levels[0]]))
+                continue
+            canvas = torch.zeros((num_imgs, pack.height, pack.width), dtype=torch.bool, device=or_feat.device)
+            for i, (h, w), (r0, c0) in zip(levels, pack.sizes, pack.places):
+                canvas[:, r0:r0 + h, c0:c0 + w] = flags[i].view(num_imgs, h, w)
+            tower = CI.rows_tower(convs, or_feat, canvas, pack.row_mask(num_imgs))
+            for i, b in zip(levels, pack.unpack(conv_module(self.odm_reg, tower))):
+                odm_box[i] = b
+        return self.loss(fam_cls, fam_box, refine, odm_cls, odm_box, gt_bboxes, gt_labels, img_metas,
+                         gt_bboxes_ignore, odm_targets=odm_targets)
+
     def forward(self, feats, targets):
+        if self._rows_forward_route(feats):
+            return self._forward_train_rows(feats, targets)
         outs = self._level_outputs(feats)
         if self.training:
             return self.loss(*outs, *self.parse_targets(targets))

@@ -377,6 +377,109 @@ def _rows_backward(g, x, weight, need_x, need_w):
     return gx, gw
 
 
+# Row-sparse FORWARD of a tower whose output only a positives-only loss reads (csrc/conv_rows.hip: jdet_rows_from_flags,
+# jdet_conv3x3_rows_forward; profiles/conv_rows_fwd.md): the S2ANet head's ODM regression tower in training.  The layers
+# are computed on the rows that feed a flagged position and are zero elsewhere; the backward is `_rows_backward`, so
+# JDET_CONV_ROWS=0 switches the route off together with it, JDET_CONV_ROWS_FWD=0 the forward route alone (A/B).
+ROWS_FWD = os.environ.get("JDET_CONV_ROWS_FWD", "1") == "1"
+
+
+def rows_forward_supported(cin, cout):
+    return bool(L.lib().jdet_conv3x3_rows_forward_supported(int(cin), int(cout)))
+
+
+def rows_from_flags(flags, N, H, W):
+    """flags: N*H*W bytes (uint8 / bool device tensor), non-zero = listed -> (rows, rows_dilated, rows_dilated2 (P,) int32,
+    counts (3,) int32): the flagged positions, ascending, their 3x3 dilation inside each image and the dilation of that;
+    list entries past their count are -1.  Everything stays on the device.  The four results are views of one fresh
+    buffer (under graph capture: of the capturing graph's pool)."""
+    L.need_device(flags)
+    P = N * H * W
+    if flags.numel() != P or flags.element_size() != 1 or not flags.is_contiguous():
+        raise ValueError("flags must be %d contiguous bytes, got %r %s" % (P, tuple(flags.shape), flags.dtype))
+    wsb = L.lib().jdet_rows_from_flags_workspace(N, H, W)
+    buf = torch.empty((12 * P + 16 + wsb,), dtype=torch.uint8, device=flags.device)
+    rows = [buf[4 * i * P:4 * (i + 1) * P].view(torch.int32) for i in range(3)]
+    counts = buf[12 * P:12 * P + 12].view(torch.int32)
+    ws = buf[12 * P + 16:]
+    L.check(L.lib().jdet_rows_from_flags(L.ptr(flags), N, H, W, L.ptr(rows[0]), L.ptr(rows[1]), L.ptr(rows[2]),
+                                         L.ptr(counts), L.ptr(ws), wsb, L.stream_ptr(flags)), "jdet_rows_from_flags")
+    return rows[0], rows[1], rows[2], counts
+
+
+def conv3x3_rows_forward_nhwc(x_nhwc, w_krsc, bias, relu, rowmask, rows, count_ptr, out=None):
+    """x (N,H,W,Cin), w (Cout,3,3,Cin), rows: int32 device list, count_ptr: device address of its length -> y
+    (N,H,W,Cout): [relu](conv + bias) * rowmask on the listed rows, all others zero.  `out`: only its listed rows are
+    written."""
+    L.need_device(x_nhwc, w_krsc, bias, rowmask, rows, out)
+    N, H, W, Cin = x_nhwc.shape
+    Cout = w_krsc.shape[0]
+    if tuple(w_krsc.shape[1:]) != (3, 3, Cin):
+        raise ValueError("weight %r does not match input channels %d" % (tuple(w_krsc.shape), Cin))
+    x_nhwc, w_krsc = L.f32c(x_nhwc), L.f32c(w_krsc)
+    zero = out is None
+    if zero:
+        out = torch.empty((N, H, W, Cout), dtype=torch.float32, device=x_nhwc.device)
+    L.check(L.lib().jdet_conv3x3_rows_forward(
+        L.ptr(x_nhwc), L.ptr(w_krsc), L.ptr(L.f32c(bias)) if bias is not None else None, int(bool(relu)),
+        L.ptr(L.f32c(rowmask)) if rowmask is not None else None, L.ptr(rows), count_ptr, N, H, W, Cin, Cout, int(zero),
+        L.ptr(out), L.stream_ptr(x_nhwc)), "jdet_conv3x3_rows_forward")
+    return out
+
+
+class _ConvBiasActRows(torch.autograd.Function):
+    """y = [relu](conv3x3(x, w) + b) [* rowmask] on the listed rows, 0 on every other row.  It saves what `_ConvBiasAct`
+    saves and its backward IS that one's rows branch: exact wherever the incoming gradient is zero outside the rows
+    whose 3x3 neighbourhoods the list covers (a row that holds 0 has the ReLU mask [y > 0] = 0, as a masked row has)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, relu, rowmask, rows, count_ptr):
+        y = conv3x3_rows_forward_nhwc(L.f32c(x.permute(0, 2, 3, 1)), weight_krsc(weight), bias, relu, rowmask, rows,
+                                      count_ptr).permute(0, 3, 1, 2)
+        ctx.k1 = False
+        ctx.row_sparse = True
+        ctx.cfg = (bool(relu), [1, 1], [1, 1], [1, 1], 1, True, bias is not None)
+        ctx.save_for_backward(x, weight, y if relu else None)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        return _ConvBiasAct.backward(ctx, g)[:7]
+
+
+def rows_tower_applicable(convs, x, positions=None):
+    """can `rows_tower` run these layers on `x` (N, C, H, W) [or on a map of `positions` rows like it]?  At most two plain 3x3 / stride 1 / pad 1 nn.Conv2d layers
+    with a trained bias (the one-pass bias backward supplies the ReLU mask), fp32 on the device, channel counts the
+    gathered tile takes, both switches on."""
+    if not (ROWS and ROWS_FWD and TRAIN and BIAS_ACT_BWD and 1 <= len(convs) <= 2):
+        return False
+    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4) or torch.is_autocast_enabled():
+        return False
+    for conv in convs:
+        if not (type(conv).__name__ == "Conv2d" and conv.padding_mode == "zeros" and not isinstance(conv.padding, str)
+                and _is_igemm_conv(conv) and conv.weight.dtype == torch.float32 and conv.bias is not None
+                and conv.bias.requires_grad and _bias_bwd_supported(conv.out_channels)
+                and rows_forward_supported(conv.in_channels, conv.out_channels)
+                and rows_supported(conv.in_channels, conv.out_channels)):
+            return False
+    P = x.shape[0] * x.shape[2] * x.shape[3] if positions is None else positions
+    return (P + 16) * max([c.in_channels for c in convs] + [c.out_channels for c in convs]) < 2 ** 30
+
+
+def rows_tower(convs, x, flags, rowmask=None):
+    """relu(conv(.)) [* rowmask] through one or two layers, computed only where the result feeds a 3x3 layer read at the
+    flagged positions: the LAST layer on the 3x3 dilation of the flags, the one before it on the dilation of that; every
+    other row of the result is zero.  flags: one byte per position of x (N*H*W), on the device."""
+    N, _, H, W = x.shape
+    lists = rows_from_flags(flags, N, H, W)
+    counts = lists[3]
+    n = len(convs)
+    for i, conv in enumerate(convs):
+        k = n - i                                   # dilations this layer's output is needed on
+        x = _ConvBiasActRows.apply(x, conv.weight, conv.bias, True, rowmask, lists[k], counts.data_ptr() + 4 * k)
+    return x
+
+
 CONV1X1_GEMM = os.environ.get("JDET_CONV1X1_GEMM", "1") == "1"
 
 
