@@ -497,6 +497,9 @@ JO_API void jo_nms_rotated(const float* dets, int n, int box_len, const int32_t*
     int i = order[_i];
     if (suppressed[i] == 1) continue;
     keep[i] = 1;
+    // the later boxes are independent of each other (every thread writes its own suppressed[j]): same flags, and a
+    // threshold that keeps nearly everything (n^2 / 2 IoUs) no longer takes ~10 s at the detectors' 8.5 k boxes
+#pragma omp parallel for schedule(static) if (n - _i > 1024)
     for (int _j = _i + 1; _j < n; _j++) {
       int j = order[_j];
       if (suppressed[j] == 1) continue;
