@@ -182,6 +182,14 @@ FCOS_SIGNATURES = {
     "jdet_poly_iou_loss": (_i, [_p, _p, _p, _l, _i, _f, _p, _p, _p]),
 }
 
+# include/jdet_hip_reppoints.h (csrc/convex_point_assign.hip, csrc/convex_giou_loss.hip; same library, a table of its own
+# for the reason ATSS_SIGNATURES has one; tests/test_reppoints_cpu.py checks it against the header and the exports)
+REPPOINTS_SIGNATURES = {
+    "jdet_convex_point_assign_workspace": (_sz, [_i, _i]),
+    "jdet_convex_point_assign": (_i, [_p, _i, _i, _p, _p, _i, _p, _p, _p, _i, _i, _f, _i, _i, _p, _p, _p, _sz, _p]),
+    "jdet_convex_giou_loss": (_i, [_p, _p, _p, _p, _l, _p, _p, _p]),
+}
+
 _lib = None
 
 # Hull-point ordering inside the rotated IoU: 0 = the reference's CPU path (std::sort,
@@ -213,7 +221,7 @@ def lib():
         # streams and allocations.
         l = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in list(SIGNATURES.items()) + list(ATSS_SIGNATURES.items()) + list(ROWS_SIGNATURES.items()) + \
-                list(ROWS_FWD_SIGNATURES.items()) + list(FCOS_SIGNATURES.items()):
+                list(ROWS_FWD_SIGNATURES.items()) + list(FCOS_SIGNATURES.items()) + list(REPPOINTS_SIGNATURES.items()):
             fn = getattr(l, name)  # AttributeError here == ABI drift: fail loudly
             fn.restype = res
             fn.argtypes = args

@@ -197,6 +197,37 @@ FCOS_CFG = dict(
     scheduler=dict(type="StepLR", warmup="linear", warmup_iters=500, warmup_ratio=1.0 / 3, milestones=[8, 11]))
 
 
+REPPOINTS_CFG = dict(
+    # configs/rotated_reppoints_obb_r50_fpn_1x_dota.py: model L2-65, optimizer L138-146, scheduler L148-153
+    # (tests/golden/configs/rotated_reppoints_obb_r50_fpn_1x_dota.yaml holds them as `Config` reads them).  Anchor-free:
+    # nine points per location, twice; init targets by jdet_convex_point_assign, refine targets by jdet_convex_iou +
+    # jdet_assign_max_iou, both point losses the convex GIoU (jdet_convex_giou_loss); GroupNorm in the FPN and the towers.
+    model=dict(
+        type="RotatedRetinaNet",
+        backbone=dict(type="Resnet50", frozen_stages=1, return_stages=["layer1", "layer2", "layer3", "layer4"],
+                      pretrained=True),
+        neck=dict(type="FPN", in_channels=[256, 512, 1024, 2048], out_channels=256, start_level=1,
+                  add_extra_convs="on_input", norm_cfg=dict(type="GN", num_groups=32), num_outs=5),
+        bbox_head=dict(
+            type="RotatedRepPointsHead", num_classes=15, in_channels=256, feat_channels=256, point_feat_channels=256,
+            stacked_convs=3, num_points=9, gradient_mul=0.3, point_strides=[8, 16, 32, 64, 128], point_base_scale=2,
+            norm_cfg=dict(type="GN", num_groups=32),
+            loss_cls=dict(type="FocalLoss", use_sigmoid=True, gamma=2.0, alpha=0.25, loss_weight=1.0),
+            loss_bbox_init=dict(type="ConvexGIoULoss", loss_weight=0.375),
+            loss_bbox_refine=dict(type="ConvexGIoULoss", loss_weight=1.0),
+            transform_method="rotrect", use_reassign=False, topk=6, anti_factor=0.75,
+            train_cfg=dict(
+                init=dict(assigner=dict(type="ConvexAssigner", scale=4, pos_num=1, assigned_labels_filled=-1),
+                          allowed_border=-1, pos_weight=-1, debug=False),
+                refine=dict(assigner=dict(type="MaxConvexIoUAssigner", pos_iou_thr=0.4, neg_iou_thr=0.3, min_pos_iou=0,
+                                          ignore_iof_thr=-1, assigned_labels_filled=-1,
+                                          iou_calculator=dict(type="ConvexOverlaps")),
+                            allowed_border=-1, pos_weight=-1, debug=False)),
+            test_cfg=dict(nms_pre=2000, min_bbox_size=0, score_thr=0.05, nms=dict(iou_thr=0.4), max_per_img=2000))),
+    optimizer=dict(type="SGD", lr=0.008, momentum=0.9, weight_decay=0.0001, grad_clip=dict(max_norm=35, norm_type=2)),
+    scheduler=dict(type="StepLR", warmup="linear", warmup_iters=500, warmup_ratio=1.0 / 3, milestones=[7, 10]))
+
+
 GLIDING_CFG = dict(
     # configs/gliding_r50_fpn_1x_dota_with_flip.py: model L2-116, optimizer L195, scheduler L197-202
     # (tests/golden/configs/gliding_r50_fpn_1x_dota_with_flip.yaml holds them as `Config` reads them)

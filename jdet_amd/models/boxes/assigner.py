@@ -1,10 +1,13 @@
 """Max-IoU and ATSS assignment.  Mirrors python/jdet/models/boxes/assigner.py: `AssignResult` L53-65,
-`MaxIoUAssigner` L67-219, `MaxIoUAssignerRbbox` L222-274, `ATSSAssignerRbbox` L276-391.
+`MaxIoUAssigner` L67-219, `MaxIoUAssignerRbbox` L222-274, `ATSSAssignerRbbox` L276-391, `ConvexAssigner` L393-548,
+`MaxConvexIoUAssigner` L550-611.
 
 `assign_wrt_overlaps` is the reference's four steps (default -1; negatives; positives; low-quality
 matches, later gts overwriting earlier ones) executed as two device launches without a host sync
 (csrc/box_codec_assign.hip) instead of the reference's per-gt Python loop with `jt.sync_all()`.  `ATSSAssignerRbbox.assign` is one fused entry
 point (csrc/atss_assign.hip, three launches) that evaluates the K x (levels x topk) candidate pairs only.
+`ConvexAssigner.assign` is one fused entry point too (csrc/convex_point_assign.hip, three launches for a whole batch)
+instead of the reference's host loop over the gts.
 """
 import math
 
@@ -168,3 +171,107 @@ class ATSSAssignerRbbox:
         gt_inds, max_overlaps, labels = atss_assign_device(
             bboxes, num_level_bboxes, gt_bboxes, self.topk, gt_labels, self.assigned_labels_filled, overlaps)
         return AssignResult(gt_bboxes.shape[0], gt_inds, max_overlaps, labels=labels)
+
+
+def convex_point_assign_device(points, num_level_points, level_ids, gt, gt_labels, gt_count, scale, pos_num,
+                               labels_filled=0):
+    """jdet_convex_point_assign on device tensors: points (N, >= 2) of all levels (shared by the images), gt
+    (B, Kmax, 8) polygons, gt_labels (B, Kmax) int32 | None, gt_count (B) int32 -> (gt_inds int32 (B, N), labels int32
+    (B, N) | None).  No host sync: the level sizes and ids (log2 of the strides) are host integers."""
+    import ctypes
+    L.need_device(points, gt, gt_labels, gt_count)
+    pts, g = L.f32c(points), L.f32c(gt)
+    N, nl = pts.shape[0], len(num_level_points)
+    assert g.dim() == 3 and g.shape[2] == 8 and len(level_ids) == nl
+    B, Kmax = g.shape[0], g.shape[1]
+    if Kmax == 0:              # no gt rows at all: one unread row, so that labels still has a gt_labels array behind it
+        Kmax = 1
+        g = g.new_zeros((B, 1, 8))
+        gt_labels = torch.zeros((B, 1), dtype=torch.int32, device=g.device) if gt_labels is not None else None
+    offs = [0]
+    for n in num_level_points:
+        offs.append(offs[-1] + int(n))
+    assert offs[-1] == N, "num_level_points sums to %d, %d points" % (offs[-1], N)
+    gl = gt_labels.to(torch.int32).contiguous() if gt_labels is not None else None
+    gc = gt_count.to(torch.int32).contiguous()
+    assert gc.numel() == B and (gl is None or tuple(gl.shape) == (B, Kmax))
+    gt_inds = torch.empty((B, N), dtype=torch.int32, device=pts.device)
+    labels = torch.empty((B, N), dtype=torch.int32, device=pts.device) if gl is not None else None
+    wsb = L.lib().jdet_convex_point_assign_workspace(B, N)
+    ws = torch.empty((max(wsb, 8),), dtype=torch.uint8, device=pts.device)
+    L.check(L.lib().jdet_convex_point_assign(
+        L.ptr(pts), N, pts.shape[1], (ctypes.c_int32 * (nl + 1))(*offs), (ctypes.c_int32 * nl)(*[int(i) for i in level_ids]),
+        nl, L.ptr(g), L.ptr(gl), L.ptr(gc), B, Kmax, float(scale), int(pos_num), int(labels_filled), L.ptr(gt_inds),
+        L.ptr(labels), L.ptr(ws), wsb, L.stream_ptr(pts)), "jdet_convex_point_assign")
+    return gt_inds, labels
+
+
+def stride_level_id(stride):
+    """the integer log2 of a stride that is an exact power of two (assigner.py:L482 applies jt.log2(..).int() to such)"""
+    s = int(stride)
+    assert s > 0 and s == stride and s & (s - 1) == 0, "point strides must be powers of two, got %r" % (stride,)
+    return s.bit_length() - 1
+
+
+@BOXES.register_module()
+class ConvexAssigner:
+    """RepPoints init-stage assignment (assigner.py:L393-548): every gt claims the `pos_num` points nearest to the centre
+    of its horizontal box, in the pyramid level its size selects; a point claimed twice goes to the nearer gt.  0
+    negative, k > 0 matched to gt k - 1.  The level of a gt, the tie order and the clamp of pos_num to a level's size
+    are stated in include/jdet_hip_reppoints.h."""
+
+    def __init__(self, scale=4, pos_num=3, assigned_labels_filled=0):
+        self.scale = scale
+        self.pos_num = pos_num
+        self.assigned_labels_filled = assigned_labels_filled
+
+    @staticmethod
+    def _levels(points):
+        """(sizes, ids) of the runs of equal stride in column 2 (one host read: the general route)"""
+        strides, counts = torch.unique_consecutive(points[:, 2], return_counts=True)
+        return counts.tolist(), [stride_level_id(s) for s in strides.tolist()]
+
+    def assign(self, points, gt_rbboxes, gt_rbboxes_ignore=None, gt_labels=None, num_level_points=None,
+               level_ids=None):
+        """points (n, >= 3) rows [x, y, stride, ...] in level order, gt_rbboxes (k, 8) -> AssignResult.  The level sizes
+        and ids are read from the stride column unless the caller passes them."""
+        num_points, num_gts = points.shape[0], gt_rbboxes.shape[0]
+        if num_points == 0:
+            return AssignResult(num_gts, torch.zeros((0,), dtype=torch.int32, device=points.device), None,
+                                labels=None if gt_labels is None else torch.zeros((0,), dtype=torch.int32,
+                                                                                  device=points.device))
+        assert num_gts == 0 or gt_rbboxes.size(1) == 8, "gt_rbboxes should be (N * 8)"
+        if num_level_points is None or level_ids is None:
+            num_level_points, level_ids = self._levels(points)
+        gt = gt_rbboxes.reshape(1, num_gts, 8)
+        gl = gt_labels.reshape(1, num_gts) if gt_labels is not None else None
+        count = torch.full((1,), num_gts, dtype=torch.int32, device=points.device)
+        gt_inds, labels = self.assign_batch(points, num_level_points, level_ids, gt, gl, count)
+        return AssignResult(num_gts, gt_inds[0], None, labels=labels[0] if labels is not None else None)
+
+    def assign_batch(self, points, num_level_points, level_ids, gt, gt_labels, gt_count):
+        """all images at once (the dense route): gt (B, Kmax, 8), gt_labels (B, Kmax) | None, gt_count (B) int32 on the
+        device -> (gt_inds (B, N) int32, labels (B, N) int32 | None)"""
+        return convex_point_assign_device(points, num_level_points, level_ids, gt, gt_labels, gt_count, self.scale,
+                                          self.pos_num, self.assigned_labels_filled)
+
+
+@BOXES.register_module()
+class MaxConvexIoUAssigner(MaxIoUAssigner):
+    """MaxIoUAssigner over point sets (n, 18) and gt polygons (k, 8) (assigner.py:L550-611): the overlaps come from
+    `ConvexOverlaps` (jdet_convex_iou), the four steps from jdet_assign_max_iou."""
+
+    def __init__(self, pos_iou_thr, neg_iou_thr, min_pos_iou=.0, gt_max_assign_all=True, ignore_iof_thr=-1,
+                 ignore_wrt_candidates=True, match_low_quality=True, assigned_labels_filled=0,
+                 iou_calculator=dict(type="ConvexOverlaps")):
+        super().__init__(pos_iou_thr=pos_iou_thr, neg_iou_thr=neg_iou_thr, min_pos_iou=min_pos_iou,
+                         gt_max_assign_all=gt_max_assign_all, ignore_iof_thr=ignore_iof_thr,
+                         ignore_wrt_candidates=ignore_wrt_candidates, match_low_quality=match_low_quality,
+                         assigned_labels_filled=assigned_labels_filled, iou_calculator=iou_calculator)
+
+    def assign(self, bboxes, gt_bboxes, gt_bboxes_ignore=None, gt_labels=None):
+        if bboxes.shape[0] == 0 or gt_bboxes.shape[0] == 0:
+            raise ValueError("No gt or bboxes")
+        overlaps = self.iou_calculator(gt_bboxes, bboxes)
+        # the reference's ignore branch is `assert NotImplementedError` (a no-op), assigner.py:L607-609
+        return self.assign_wrt_overlaps(overlaps, gt_labels)

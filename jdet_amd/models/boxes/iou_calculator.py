@@ -1,6 +1,7 @@
 """IoU calculators resolved by name through the BOXES registry.  Mirrors
 python/jdet/models/boxes/iou_calculator.py: `BboxOverlaps2D_rotated` L121-159 (-> box_iou_rotated),
-`BboxOverlaps2D_rotated_v1` L161-198 (-> box_iou_rotated_v1), `bbox_overlaps_rotated` L228-233."""
+`BboxOverlaps2D_rotated_v1` L161-198 (-> box_iou_rotated_v1), `ConvexOverlaps` L199-226 (-> reppoints_convex_iou),
+`bbox_overlaps_rotated` L228-233."""
 from jdet_amd.ops import box_iou_rotated, box_iou_rotated_v1
 from jdet_amd.utils.registry import BOXES
 
@@ -69,6 +70,22 @@ class FakeBboxOverlaps2D_rotated:
         bboxes2 = fake_rotated_boxes(bboxes2)
         assert mode == "iou" and is_aligned is False
         return bbox_overlaps_rotated(bboxes1, bboxes2)
+
+    def __repr__(self):
+        return self.__class__.__name__ + "()"
+
+
+@BOXES.register_module()
+class ConvexOverlaps:
+    """IoU between polygons (m, 8) and the convex hulls of point sets (n, 18) -> (m, n): the transpose of
+    `reppoints_convex_iou` (iou_calculator.py:L199-226 of the reference).  Only mode='iou', not aligned."""
+
+    def __call__(self, bboxes, pointsets, mode="iou", is_aligned=False):
+        from jdet_amd.ops.reppoints_convex_iou import reppoints_convex_iou
+        assert bboxes.shape[-1] == 8
+        assert pointsets.shape[-1] == 18
+        assert mode == "iou" and is_aligned is False
+        return reppoints_convex_iou(pointsets, bboxes).t()
 
     def __repr__(self):
         return self.__class__.__name__ + "()"

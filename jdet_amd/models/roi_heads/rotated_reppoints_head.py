@@ -1,0 +1,654 @@
+"""Rotated RepPoints head (anchor-free, point-set representation).  Mirrors
+python/jdet/models/roi_heads/rotated_reppoints_head.py: RotatedRepPointsHead L72-1263 (constructor arguments and layer
+names are the reference's, so its checkpoints map by name), MlvlPointGenerator L1328-1538.  Every location predicts
+nine points twice (init, refine) through a deformable conv whose offsets ARE the init points; a point set becomes a box
+by the minimum-area rectangle of its hull (jdet_min_area_bbox); both point losses are the convex GIoU.
+
+Two routes for targets and losses, same values:
+  dense    every point valid (`_all_valid`), no ignore boxes, PseudoSampler, ConvexAssigner for the init stage and
+           MaxConvexIoUAssigner for the refine stage, device fp32 tensors -- what the config hits.  ONE
+           jdet_convex_point_assign per step for all images, the refine assignment per image through jdet_convex_iou +
+           jdet_assign_max_iou, ONE jdet_convex_giou_loss per stage over all rows; the targets are `where` / `gather`
+           over (B, N) arrays and both positive counts stay device tensors: no nonzero(), no host sync.
+  general  the reference's: inside flags, the assigners per image, PseudoSampler's index lists, `unmap`, the positives
+           of every (level, stage) gathered through nonzero().
+
+Not the reference's, on purpose:
+  - `use_reassign=True` (the CFA branch: get_cfa_targets, get_pos_loss, reassign) raises NotImplementedError.
+  - pad_shape is stored (w, h) in this project; the head hands MlvlPointGenerator.valid_flags (h, w).
+  - a refine-stage image without gts is all negative (the reference's MaxConvexIoUAssigner raises there).
+  - the final polygons -> OBB conversion before NMS is `rectpoly2obb` on the device: the polygons are the exact
+    rectangles of jdet_min_area_bbox, so the reference's host round trip through cv2.minAreaRect is not needed.
+  - init_weights: normal(0, 0.01) for every conv, the classification bias at prior probability 0.01 (the public
+    mmrotate head's initialisation; the reference leaves the framework's defaults)."""
+import numpy as np
+import torch
+from torch import nn
+
+from jdet_amd.models.boxes.anchor_target import images_to_levels
+from jdet_amd.models.boxes.assigner import (AssignResult, ConvexAssigner, MaxConvexIoUAssigner,
+                                            assign_wrt_overlaps_device, stride_level_id)
+from jdet_amd.models.boxes.box_ops import rotated_box_to_poly
+from jdet_amd.models.boxes.sampler import PseudoSampler
+from jdet_amd.models.losses.convex_giou_loss import ConvexGIoULoss
+from jdet_amd.models.utils.modules import ConvModule
+from jdet_amd.models.utils.weight_init import bias_init_with_prob, normal_init
+from jdet_amd.ops.bbox_transforms import obb2poly, rectpoly2obb
+from jdet_amd.ops.dcn_v1 import DeformConv
+from jdet_amd.ops.nms_rotated import multiclass_nms_rotated
+from jdet_amd.ops.reppoints_min_area_bbox import reppoints_min_area_bbox
+from jdet_amd.utils.general import multi_apply, unmap
+from jdet_amd.utils.registry import BOXES, HEADS, LOSSES, build_from_cfg
+
+from .fcos_head import _device_counts
+from .s2anet_head import _cfg
+
+
+def _pair(x):
+    return tuple(x) if isinstance(x, (tuple, list)) else (x, x)
+
+
+class MlvlPointGenerator:
+    """grid points of every pyramid level (L1328-1538): point (x, y) of cell (i, j) is ((j + offset) * stride_w,
+    (i + offset) * stride_h), row-major; `with_stride` appends (stride_w, stride_h)."""
+
+    def __init__(self, strides, offset=0.5):
+        self.strides = [_pair(stride) for stride in strides]
+        self.offset = offset
+
+    @property
+    def num_levels(self):
+        return len(self.strides)
+
+    @property
+    def num_base_priors(self):
+        return [1 for _ in range(len(self.strides))]
+
+    def _meshgrid(self, x, y, row_major=True):
+        yy, xx = torch.meshgrid(y, x, indexing="ij")
+        if row_major:
+            return xx.reshape(-1), yy.reshape(-1)
+        return yy.reshape(-1), xx.reshape(-1)
+
+    def grid_priors(self, featmap_sizes, dtype=torch.float32, device=None, with_stride=False):
+        assert self.num_levels == len(featmap_sizes)
+        return [self.single_level_grid_priors(featmap_sizes[i], level_idx=i, dtype=dtype, device=device,
+                                              with_stride=with_stride) for i in range(self.num_levels)]
+
+    def single_level_grid_priors(self, featmap_size, level_idx, dtype=torch.float32, device=None, with_stride=False):
+        feat_h, feat_w = featmap_size
+        stride_w, stride_h = self.strides[level_idx]
+        shift_x = ((torch.arange(0, feat_w, device=device) + self.offset) * stride_w).to(dtype)
+        shift_y = ((torch.arange(0, feat_h, device=device) + self.offset) * stride_h).to(dtype)
+        shift_xx, shift_yy = self._meshgrid(shift_x, shift_y)
+        if not with_stride:
+            return torch.stack([shift_xx, shift_yy], dim=-1)
+        stride_w = torch.full((shift_xx.shape[0],), stride_w, dtype=dtype, device=device)
+        stride_h = torch.full((shift_yy.shape[0],), stride_h, dtype=dtype, device=device)
+        return torch.stack([shift_xx, shift_yy, stride_w, stride_h], dim=-1)
+
+    def valid_flags(self, featmap_sizes, pad_shape, device=None):
+        """pad_shape: (h, w)"""
+        assert self.num_levels == len(featmap_sizes)
+        multi_level_flags = []
+        for i in range(self.num_levels):
+            point_stride = self.strides[i]
+            feat_h, feat_w = featmap_sizes[i]
+            h, w = pad_shape[:2]
+            valid_feat_h = min(int(np.ceil(h / point_stride[1])), feat_h)
+            valid_feat_w = min(int(np.ceil(w / point_stride[0])), feat_w)
+            multi_level_flags.append(self.single_level_valid_flags((feat_h, feat_w), (valid_feat_h, valid_feat_w),
+                                                                   device=device))
+        return multi_level_flags
+
+    def single_level_valid_flags(self, featmap_size, valid_size, device=None):
+        feat_h, feat_w = featmap_size
+        valid_h, valid_w = valid_size
+        assert valid_h <= feat_h and valid_w <= feat_w
+        valid_x = torch.zeros(feat_w, dtype=torch.bool, device=device)
+        valid_y = torch.zeros(feat_h, dtype=torch.bool, device=device)
+        valid_x[:valid_w] = 1
+        valid_y[:valid_h] = 1
+        valid_xx, valid_yy = self._meshgrid(valid_x, valid_y)
+        return valid_xx & valid_yy
+
+    def sparse_priors(self, prior_idxs, featmap_size, level_idx, dtype=torch.float32):
+        height, width = featmap_size
+        x = (prior_idxs % width + self.offset) * self.strides[level_idx][0]
+        y = ((prior_idxs // width) % height + self.offset) * self.strides[level_idx][1]
+        return torch.stack([x, y], 1).to(dtype)
+
+
+@HEADS.register_module()
+class RotatedRepPointsHead(nn.Module):
+    def __init__(self, num_classes, in_channels, feat_channels, point_feat_channels=256, stacked_convs=3, num_points=9,
+                 gradient_mul=0.1, point_strides=[8, 16, 32, 64, 128], point_base_scale=4, background_label=0,
+                 conv_bias="auto",
+                 loss_cls=dict(type="FocalLoss", use_sigmoid=True, gamma=2.0, alpha=0.25, loss_weight=1.0),
+                 loss_bbox_init=dict(type="SmoothL1Loss", beta=1.0 / 9.0, loss_weight=0.5),
+                 loss_bbox_refine=dict(type="SmoothL1Loss", beta=1.0 / 9.0, loss_weight=1.0),
+                 conv_cfg=None, norm_cfg=None, train_cfg=None, test_cfg=None, center_init=True,
+                 transform_method="rotrect", use_reassign=False, topk=6, anti_factor=0.75, **kwargs):
+        super().__init__()
+        if use_reassign:
+            raise NotImplementedError(
+                "RotatedRepPointsHead: use_reassign=True (the CFA branch: get_cfa_targets, get_pos_loss, reassign) is "
+                "not ported; only the plain RepPoints assignment (use_reassign=False) is")
+        self.num_points = num_points
+        self.point_feat_channels = point_feat_channels
+        self.center_init = center_init
+        # the deformable conv samples the feature at the points
+        self.dcn_kernel = int(np.sqrt(num_points))
+        self.dcn_pad = int((self.dcn_kernel - 1) / 2)
+        assert self.dcn_kernel * self.dcn_kernel == num_points, "The points number should be a square number."
+        assert self.dcn_kernel % 2 == 1, "The points number should be an odd square number."
+        dcn_base = np.arange(-self.dcn_pad, self.dcn_pad + 1).astype(np.float64)
+        dcn_base_y = np.repeat(dcn_base, self.dcn_kernel)
+        dcn_base_x = np.tile(dcn_base, self.dcn_kernel)
+        dcn_base_offset = np.stack([dcn_base_y, dcn_base_x], axis=1).reshape((-1))
+        self.register_buffer("dcn_base_offset", torch.tensor(dcn_base_offset, dtype=torch.float32).view(1, -1, 1, 1),
+                             persistent=False)
+        self.num_classes = num_classes
+        self.in_channels = in_channels
+        self.feat_channels = feat_channels
+        self.stacked_convs = stacked_convs
+        assert conv_bias == "auto" or isinstance(conv_bias, bool)
+        self.conv_bias = conv_bias
+        self.loss_cls = build_from_cfg(loss_cls, LOSSES)
+        self.train_cfg = _cfg(train_cfg)
+        self.test_cfg = _cfg(test_cfg)
+        self.conv_cfg = conv_cfg
+        # (`is_train` is a Jittor GroupNorm argument)
+        self.norm_cfg = {k: v for k, v in norm_cfg.items() if k != "is_train"} if norm_cfg is not None else None
+        self.gradient_mul = gradient_mul
+        self.point_base_scale = point_base_scale
+        self.point_strides = list(point_strides)
+        self.prior_generator = MlvlPointGenerator(self.point_strides, offset=0.)
+        self.num_base_priors = self.prior_generator.num_base_priors[0]
+        self.sampling = loss_cls["type"] not in ["FocalLoss"]
+        if self.train_cfg:
+            self.init_assigner = build_from_cfg(self.train_cfg.init.assigner, BOXES)
+            self.refine_assigner = build_from_cfg(self.train_cfg.refine.assigner, BOXES)
+            if self.sampling and hasattr(self.train_cfg, "sampler"):
+                sampler_cfg = self.train_cfg.sampler
+            else:
+                sampler_cfg = dict(type="PseudoSampler")
+            self.sampler = build_from_cfg(sampler_cfg, BOXES)
+        self.transform_method = transform_method
+        self.use_sigmoid_cls = loss_cls.get("use_sigmoid", False)
+        self.cls_out_channels = self.num_classes if self.use_sigmoid_cls else self.num_classes + 1
+        self.loss_bbox_init = build_from_cfg(loss_bbox_init, LOSSES)
+        self.loss_bbox_refine = build_from_cfg(loss_bbox_refine, LOSSES)
+        self.use_reassign = use_reassign
+        self.topk = topk
+        self.anti_factor = anti_factor
+        self.background_label = background_label
+        self.dense = True               # A/B switch of the two routes (tests)
+        self._cache = {}
+        self._init_layers()
+        self.init_weights()
+
+    def _init_layers(self):
+        self.relu = nn.ReLU()
+        self.cls_convs = nn.ModuleList()
+        self.reg_convs = nn.ModuleList()
+        for i in range(self.stacked_convs):
+            chn = self.in_channels if i == 0 else self.feat_channels
+            self.cls_convs.append(ConvModule(chn, self.feat_channels, 3, stride=1, padding=1, conv_cfg=self.conv_cfg,
+                                             norm_cfg=self.norm_cfg, bias=self.conv_bias))
+            self.reg_convs.append(ConvModule(chn, self.feat_channels, 3, stride=1, padding=1, conv_cfg=self.conv_cfg,
+                                             norm_cfg=self.norm_cfg, bias=self.conv_bias))
+        pts_out_dim = 2 * self.num_points
+        self.reppoints_cls_conv = DeformConv(self.feat_channels, self.point_feat_channels, self.dcn_kernel, 1,
+                                             self.dcn_pad)
+        self.reppoints_cls_out = nn.Conv2d(self.point_feat_channels, self.cls_out_channels, 1, 1, 0)
+        self.reppoints_pts_init_conv = nn.Conv2d(self.feat_channels, self.point_feat_channels, 3, 1, 1)
+        self.reppoints_pts_init_out = nn.Conv2d(self.point_feat_channels, pts_out_dim, 1, 1, 0)
+        self.reppoints_pts_refine_conv = DeformConv(self.feat_channels, self.point_feat_channels, self.dcn_kernel, 1,
+                                                    self.dcn_pad)
+        self.reppoints_pts_refine_out = nn.Conv2d(self.point_feat_channels, pts_out_dim, 1, 1, 0)
+
+    def init_weights(self):
+        for m in self.cls_convs:
+            normal_init(m.conv, std=0.01)
+        for m in self.reg_convs:
+            normal_init(m.conv, std=0.01)
+        bias_cls = bias_init_with_prob(0.01)
+        nn.init.normal_(self.reppoints_cls_conv.weight, 0, 0.01)
+        normal_init(self.reppoints_cls_out, std=0.01, bias=bias_cls)
+        normal_init(self.reppoints_pts_init_conv, std=0.01)
+        normal_init(self.reppoints_pts_init_out, std=0.01)
+        nn.init.normal_(self.reppoints_pts_refine_conv.weight, 0, 0.01)
+        normal_init(self.reppoints_pts_refine_out, std=0.01)
+
+    def points2rotrect(self, pts, y_first=True):
+        """point sets -> the four corners of their minimum-area rectangle (n, 8)"""
+        if y_first:
+            pts = pts.reshape(-1, self.num_points, 2)
+            pts_dy = pts[:, :, 0::2]
+            pts_dx = pts[:, :, 1::2]
+            pts = torch.cat([pts_dx, pts_dy], dim=2).reshape(-1, 2 * self.num_points)
+        if self.transform_method == "rotrect":
+            return reppoints_min_area_bbox(pts)
+        raise NotImplementedError
+
+    def forward_single(self, x):
+        dcn_base_offset = self.dcn_base_offset.to(x.dtype)
+        points_init = 0
+        cls_feat = x
+        pts_feat = x
+        for cls_conv in self.cls_convs:
+            cls_feat = cls_conv(cls_feat)
+        for reg_conv in self.reg_convs:
+            pts_feat = reg_conv(pts_feat)
+        # initialize reppoints
+        pts_out_init = self.reppoints_pts_init_out(self.relu(self.reppoints_pts_init_conv(pts_feat)))
+        pts_out_init = pts_out_init + points_init
+        # refine and classify reppoints
+        pts_out_init_grad_mul = (1 - self.gradient_mul) * pts_out_init.detach() + self.gradient_mul * pts_out_init
+        dcn_offset = pts_out_init_grad_mul - dcn_base_offset
+        cls_out = self.reppoints_cls_out(self.relu(self.reppoints_cls_conv(cls_feat, dcn_offset)))
+        pts_out_refine = self.reppoints_pts_refine_out(self.relu(self.reppoints_pts_refine_conv(pts_feat, dcn_offset)))
+        pts_out_refine = pts_out_refine + pts_out_init.detach()
+        return cls_out, pts_out_init, pts_out_refine
+
+    # ------------------------------------------------------------------------------------------------ points, targets
+    def get_points(self, featmap_sizes, img_metas, device=None):
+        """(points of each image, valid flags of each image); the grids depend on the level sizes only and are cached.
+        Sets img_meta["_all_valid"], a host-side fact (no device sync)."""
+        key = ("points", tuple(featmap_sizes), str(device))
+        if key not in self._cache:
+            self._cache[key] = self.prior_generator.grid_priors(featmap_sizes, device=device, with_stride=True)
+        multi_level_points = self._cache[key]
+        points_list = [list(multi_level_points) for _ in range(len(img_metas))]
+        valid_flag_list = []
+        for img_meta in img_metas:
+            w, h = img_meta["pad_shape"][:2]
+            key = ("flags", tuple(featmap_sizes), (h, w), str(device))
+            if key not in self._cache:
+                flags = self.prior_generator.valid_flags(featmap_sizes, (h, w), device=device)
+                all_valid = all(int(np.ceil(h / s[1])) >= fh and int(np.ceil(w / s[0])) >= fw
+                                for s, (fh, fw) in zip(self.prior_generator.strides, featmap_sizes))
+                self._cache[key] = (flags, all_valid)
+            flags, all_valid = self._cache[key]
+            img_meta["_all_valid"] = all_valid
+            valid_flag_list.append(list(flags))
+        return points_list, valid_flag_list
+
+    def offset_to_pts(self, center_list, pred_list):
+        """per level (B, H * W, 18) xy point coordinates from the (B, 18, H, W) y-first offsets: swap to xy, times the
+        stride, plus the cell's point (L302-319; the images of a batch share their grid, so a level is one expression)"""
+        pts_list = []
+        for i_lvl, stride in enumerate(self.point_strides):
+            pts_shift = pred_list[i_lvl]
+            B = pts_shift.shape[0]
+            pts_center = center_list[0][i_lvl][:, :2].repeat(1, self.num_points)
+            yx_pts_shift = pts_shift.permute(0, 2, 3, 1).reshape(B, -1, 2 * self.num_points)
+            y_pts_shift = yx_pts_shift[..., 0::2]
+            x_pts_shift = yx_pts_shift[..., 1::2]
+            xy_pts_shift = torch.stack([x_pts_shift, y_pts_shift], -1).reshape(B, -1, 2 * self.num_points)
+            pts_list.append(xy_pts_shift * stride + pts_center)
+        return pts_list
+
+    def _point_target_single(self, flat_proposals, valid_flags, gt_bboxes, gt_bboxes_ignore, gt_labels, overlaps,
+                             stage="init", unmap_outputs=True):
+        inside_flags = valid_flags
+        if not inside_flags.any():
+            return (None,) * 8
+        proposals = flat_proposals[inside_flags, :]
+        if stage == "init":
+            assigner = self.init_assigner
+            pos_weight = self.train_cfg.init.pos_weight
+        else:
+            assigner = self.refine_assigner
+            pos_weight = self.train_cfg.refine.pos_weight
+        gt_bboxes = obb2poly(gt_bboxes)
+        labels_arg = None if self.sampling else gt_labels
+        if gt_bboxes.shape[0] == 0 and stage != "init":     # (the reference's assigner raises here)
+            assign_result = AssignResult(0, torch.zeros((proposals.shape[0],), dtype=torch.int32,
+                                                        device=proposals.device), None)
+        else:
+            assign_result = assigner.assign(proposals, gt_bboxes, gt_bboxes_ignore, labels_arg)
+        sampling_result = self.sampler.sample(assign_result, proposals, gt_bboxes)
+
+        num_valid_proposals = proposals.shape[0]
+        bbox_gt = proposals.new_zeros([num_valid_proposals, 8])
+        pos_proposals = torch.zeros_like(proposals)
+        proposals_weights = proposals.new_zeros(num_valid_proposals)
+        labels = torch.full((num_valid_proposals,), self.background_label, dtype=torch.int32, device=proposals.device)
+        label_weights = torch.zeros((num_valid_proposals,), dtype=torch.float32, device=proposals.device)
+        pos_inds = sampling_result.pos_inds
+        neg_inds = sampling_result.neg_inds
+        if len(pos_inds) > 0:
+            bbox_gt[pos_inds, :] = sampling_result.pos_gt_bboxes
+            pos_proposals[pos_inds, :] = proposals[pos_inds, :]
+            proposals_weights[pos_inds] = 1.0
+            if gt_labels is None:
+                labels[pos_inds] = 1
+            else:
+                labels[pos_inds] = gt_labels[sampling_result.pos_assigned_gt_inds].to(labels.dtype)
+            label_weights[pos_inds] = 1.0 if pos_weight <= 0 else pos_weight
+        if len(neg_inds) > 0:
+            label_weights[neg_inds] = 1.0
+        if unmap_outputs:
+            num_total_proposals = flat_proposals.size(0)
+            labels = unmap(labels, num_total_proposals, inside_flags)
+            label_weights = unmap(label_weights, num_total_proposals, inside_flags)
+            bbox_gt = unmap(bbox_gt, num_total_proposals, inside_flags)
+            pos_proposals = unmap(pos_proposals, num_total_proposals, inside_flags)
+            proposals_weights = unmap(proposals_weights, num_total_proposals, inside_flags)
+        return (labels, label_weights, bbox_gt, pos_proposals, proposals_weights, pos_inds, neg_inds, sampling_result)
+
+    def _dense_ok(self, proposals, img_metas, gt_bboxes_list, gt_bboxes_ignore_list, gt_labels_list):
+        if not self.dense or self.sampling or type(self.sampler) is not PseudoSampler:
+            return False
+        if type(self.init_assigner) is not ConvexAssigner or type(self.refine_assigner) is not MaxConvexIoUAssigner:
+            return False
+        if not all(bool(m.get("_all_valid", False)) for m in img_metas):
+            return False
+        if gt_bboxes_ignore_list is not None and any(g is not None and g.numel() > 0 for g in gt_bboxes_ignore_list):
+            return False
+        if gt_labels_list is None or any(t is None or not t.is_cuda for t in gt_labels_list):
+            return False
+        return proposals.is_cuda and proposals.dtype == torch.float32 and all(
+            g.is_cuda and g.dtype == torch.float32 and g.dim() == 2 and g.shape[-1] == 5 for g in gt_bboxes_list)
+
+    @staticmethod
+    def _pad_gts(gt_polys_list, gt_labels_list):
+        """(gt (B, Kmax, 8), labels (B, Kmax) int32, counts: host list); Kmax >= 1, the rows beyond an image's count 0"""
+        B = len(gt_polys_list)
+        counts = [int(g.shape[0]) for g in gt_polys_list]
+        Kmax = max(max(counts), 1)
+        dev = gt_polys_list[0].device
+        if all(c == Kmax for c in counts):
+            return (torch.stack(gt_polys_list), torch.stack([t.to(torch.int32) for t in gt_labels_list]), counts)
+        gt = torch.zeros((B, Kmax, 8), dtype=torch.float32, device=dev)
+        gl = torch.zeros((B, Kmax), dtype=torch.int32, device=dev)
+        for b, (g, t) in enumerate(zip(gt_polys_list, gt_labels_list)):
+            if counts[b]:
+                gt[b, :counts[b]] = g
+                gl[b, :counts[b]] = t.to(torch.int32)
+        return gt, gl, counts
+
+    def _dense_stage_targets(self, gt_inds, proposals, gt, gl, pos_weight):
+        """the arrays _point_target_single builds from index lists, as `where` / `gather` over (B, N): gt_inds (B, N)
+        int32 (-1 ignored, 0 negative, g + 1), proposals (N, D) | (B, N, D), gt (B, Kmax, 8), gl (B, Kmax) ->
+        (labels, label_weights, bbox_gt, pos_proposals, proposals_weights, num_total_pos [device])"""
+        B, N = gt_inds.shape
+        pos = gt_inds > 0
+        idx = (gt_inds - 1).clamp(min=0).long()
+        labels = torch.where(pos, torch.gather(gl, 1, idx), torch.full_like(gt_inds, self.background_label))
+        w_pos = 1.0 if pos_weight <= 0 else float(pos_weight)
+        label_weights = torch.where(pos, torch.full((B, N), w_pos, dtype=torch.float32, device=gt_inds.device),
+                                    (gt_inds == 0).to(torch.float32))
+        # (`where`, not a product with the mask: 0 * a negative coordinate is -0.0)
+        picked = torch.gather(gt, 1, idx[..., None].expand(B, N, 8))
+        bbox_gt = torch.where(pos[..., None], picked, torch.zeros_like(picked))
+        if proposals.dim() == 2:
+            proposals = proposals[None].expand(B, *proposals.shape)
+        pos_proposals = torch.where(pos[..., None], proposals, torch.zeros_like(proposals))
+        proposals_weights = pos.to(torch.float32)
+        num_total_pos = pos.sum(dim=1).clamp(min=1).sum()
+        return labels, label_weights, bbox_gt, pos_proposals, proposals_weights, num_total_pos
+
+    def get_targets_dense(self, proposals_list, gt_bboxes_list, gt_labels_list, stage="init"):
+        """`get_targets` of the dense route.  init: proposals_list[0] holds the shared grid; refine: the images' point
+        sets.  Returns the seven lists / counts of `get_targets` (the counts device tensors) + None."""
+        num_level_proposals = [points.size(0) for points in proposals_list[0]]
+        gt_polys = [obb2poly(g) for g in gt_bboxes_list]
+        gt, gl, counts = self._pad_gts(gt_polys, gt_labels_list)
+        B = len(gt_polys)
+        if stage == "init":
+            points = torch.cat(proposals_list[0])
+            level_ids = [stride_level_id(s) for s in self.point_strides]
+            gt_inds, _ = self.init_assigner.assign_batch(points, num_level_proposals, level_ids, gt, None,
+                                                         _device_counts(counts, points.device))
+            proposals = points
+            pos_weight = self.train_cfg.init.pos_weight
+        else:
+            proposals = torch.stack([torch.cat(p) for p in proposals_list])
+            a = self.refine_assigner
+            inds = []
+            for b in range(B):
+                if counts[b] == 0:
+                    inds.append(torch.zeros((proposals.shape[1],), dtype=torch.int32, device=proposals.device))
+                    continue
+                overlaps = a.iou_calculator(gt_polys[b], proposals[b])
+                inds.append(assign_wrt_overlaps_device(overlaps, a.pos_iou_thr, a.neg_iou_thr, a.min_pos_iou,
+                                                       a.match_low_quality, a.gt_max_assign_all, None,
+                                                       a.assigned_labels_filled)[0])
+            gt_inds = torch.stack(inds)
+            pos_weight = self.train_cfg.refine.pos_weight
+        labels, label_weights, bbox_gt, pos_proposals, proposals_weights, num_total_pos = self._dense_stage_targets(
+            gt_inds, proposals, gt, gl, pos_weight)
+        num_total_neg = (gt_inds == 0).sum(dim=1).clamp(min=1).sum()
+        split = lambda t: list(torch.split(t, num_level_proposals, dim=1))  # noqa: E731
+        return (split(labels), split(label_weights), split(bbox_gt), split(pos_proposals), split(proposals_weights),
+                num_total_pos, num_total_neg, None)
+
+    def get_targets(self, proposals_list, valid_flag_list, gt_bboxes_list, img_metas, gt_bboxes_ignore_list=None,
+                    gt_labels_list=None, stage="init", label_channels=1, unmap_outputs=True):
+        """per level: labels, label weights, gt polygons, positive proposals, proposal weights (each (B, n_level, ..))
+        + the numbers of positives and negatives (every image counts at least 1)"""
+        assert stage in ["init", "refine"]
+        num_imgs = len(img_metas)
+        assert len(proposals_list) == len(valid_flag_list) == num_imgs
+        if self._dense_ok(proposals_list[0][0], img_metas, gt_bboxes_list, gt_bboxes_ignore_list, gt_labels_list):
+            return self.get_targets_dense(proposals_list, gt_bboxes_list, gt_labels_list, stage)
+        num_level_proposals = [points.size(0) for points in proposals_list[0]]
+        proposals_list = [torch.cat(p) for p in proposals_list]
+        valid_flag_list = [torch.cat(f) for f in valid_flag_list]
+        if gt_bboxes_ignore_list is None:
+            gt_bboxes_ignore_list = [None for _ in range(num_imgs)]
+        if gt_labels_list is None:
+            gt_labels_list = [None for _ in range(num_imgs)]
+        all_overlaps_rotate_list = [None] * len(proposals_list)
+        (all_labels, all_label_weights, all_bbox_gt, all_proposals, all_proposal_weights, pos_inds_list, neg_inds_list,
+         sampling_result) = multi_apply(self._point_target_single, proposals_list, valid_flag_list, gt_bboxes_list,
+                                        gt_bboxes_ignore_list, gt_labels_list, all_overlaps_rotate_list, stage=stage,
+                                        unmap_outputs=unmap_outputs)
+        if any([labels is None for labels in all_labels]):
+            return None
+        num_total_pos = sum([max(inds.numel(), 1) for inds in pos_inds_list])
+        num_total_neg = sum([max(inds.numel(), 1) for inds in neg_inds_list])
+        labels_list = images_to_levels(all_labels, num_level_proposals)
+        label_weights_list = images_to_levels(all_label_weights, num_level_proposals)
+        bbox_gt_list = images_to_levels(all_bbox_gt, num_level_proposals)
+        proposals_list = images_to_levels(all_proposals, num_level_proposals)
+        proposal_weights_list = images_to_levels(all_proposal_weights, num_level_proposals)
+        return (labels_list, label_weights_list, bbox_gt_list, proposals_list, proposal_weights_list, num_total_pos,
+                num_total_neg, None)
+
+    # ------------------------------------------------------------------------------------------------------------ loss
+    def _cls_loss(self, cls_score, labels, label_weights, num_total_samples_refine):
+        cls_score = cls_score.permute(0, 2, 3, 1).reshape(-1, self.cls_out_channels)
+        if torch.is_tensor(num_total_samples_refine):
+            # the level's windows of the (B, N) arrays go to the loss as they are (one node per level)
+            return self.loss_cls(cls_score, labels, label_weights,
+                                 avg_factor=num_total_samples_refine.to(torch.float32).reshape(()))
+        return self.loss_cls(cls_score, labels.reshape(-1), label_weights.reshape(-1),
+                             avg_factor=num_total_samples_refine)
+
+    def _pts_loss_general(self, loss_fn, pts_pred, rbbox_gt, convex_weights, normalize_term):
+        rbbox_gt = rbbox_gt.reshape(-1, 8)
+        convex_weights = convex_weights.reshape(-1)
+        pts_pred = pts_pred.reshape(-1, 2 * self.num_points)
+        pos_ind = (convex_weights > 0).nonzero().reshape(-1)
+        # a tensor divisor: IEEE division (a host scalar divides through its reciprocal)
+        norm = pts_pred.new_tensor(float(normalize_term))
+        return loss_fn(pts_pred[pos_ind] / norm, rbbox_gt[pos_ind] / norm, convex_weights[pos_ind])
+
+    def loss_single(self, cls_score, pts_pred_init, pts_pred_refine, labels, label_weights, rbbox_gt_init,
+                    convex_weights_init, rbbox_gt_refine, convex_weights_refine, stride, num_total_samples_refine):
+        """one level of the general route (L593-645, the use_reassign=False branch)"""
+        normalize_term = self.point_base_scale * stride
+        loss_pts_init = self._pts_loss_general(self.loss_bbox_init, pts_pred_init, rbbox_gt_init, convex_weights_init,
+                                               normalize_term)
+        loss_pts_refine = self._pts_loss_general(self.loss_bbox_refine, pts_pred_refine, rbbox_gt_refine,
+                                                 convex_weights_refine, normalize_term)
+        loss_cls = self._cls_loss(cls_score, labels, label_weights, num_total_samples_refine)
+        return loss_cls, loss_pts_init, loss_pts_refine
+
+    def _norm_rows(self, num_level_points, B, device):
+        """(B * N) normalising term of every row, image-major"""
+        key = ("norm", tuple(num_level_points), B, str(device))
+        if key not in self._cache:
+            per_point = torch.cat([torch.full((n,), float(self.point_base_scale * s), dtype=torch.float32, device=device)
+                                   for n, s in zip(num_level_points, self.point_strides)])
+            self._cache[key] = per_point.repeat(B).contiguous()
+        return self._cache[key]
+
+    def _pts_loss_dense(self, loss_fn, pts_preds, rbbox_gt_list, convex_weights_list):
+        """every level of one stage through ONE launch; the per-level means over device counts"""
+        num_level_points = [p.shape[1] for p in pts_preds]
+        B = pts_preds[0].shape[0]
+        pred = torch.cat(pts_preds, dim=1).reshape(-1, 2 * self.num_points)
+        target = torch.cat(rbbox_gt_list, dim=1).reshape(-1, 8)
+        weight = torch.cat(convex_weights_list, dim=1)
+        rows = loss_fn.dense_rows(pred, target, weight.reshape(-1), self._norm_rows(num_level_points, B, pred.device))
+        rows = rows.view(B, -1)
+        losses, start = [], 0
+        for n in num_level_points:
+            losses.append(loss_fn.reduce_dense(rows[:, start:start + n], (weight[:, start:start + n] > 0).sum()))
+            start += n
+        return losses
+
+    def loss(self, cls_scores, pts_preds_init, pts_preds_refine, gt_bboxes, gt_labels, img_metas,
+             gt_bboxes_ignore=None):
+        featmap_sizes = [tuple(featmap.shape[-2:]) for featmap in cls_scores]
+        assert len(featmap_sizes) == self.prior_generator.num_levels
+        label_channels = self.cls_out_channels if self.use_sigmoid_cls else 1
+        device = cls_scores[0].device
+        # targets of the init stage
+        center_list, valid_flag_list = self.get_points(featmap_sizes, img_metas, device)
+        pts_coordinate_preds_init = self.offset_to_pts(center_list, pts_preds_init)
+        if self.train_cfg.init.assigner["type"] == "ConvexAssigner":
+            candidate_list = center_list
+        else:
+            raise NotImplementedError
+        cls_reg_targets_init = self.get_targets(candidate_list, valid_flag_list, gt_bboxes, img_metas,
+                                                gt_bboxes_ignore_list=gt_bboxes_ignore, gt_labels_list=gt_labels,
+                                                stage="init", label_channels=label_channels)
+        if cls_reg_targets_init is None:
+            return None
+        (*_, rbbox_gt_list_init, candidate_list_init, convex_weights_list_init, num_total_pos_init, num_total_neg_init,
+         _) = cls_reg_targets_init
+        # targets of the refine stage: the init points, detached, are its proposals
+        center_list, valid_flag_list = self.get_points(featmap_sizes, img_metas, device)
+        pts_coordinate_preds_refine = self.offset_to_pts(center_list, pts_preds_refine)
+        points_list = self._refine_proposals(center_list, pts_preds_init)
+        cls_reg_targets_refine = self.get_targets(points_list, valid_flag_list, gt_bboxes, img_metas,
+                                                  gt_bboxes_ignore_list=gt_bboxes_ignore, gt_labels_list=gt_labels,
+                                                  stage="refine", label_channels=label_channels)
+        if cls_reg_targets_refine is None:
+            return None
+        (labels_list, label_weights_list, rbbox_gt_list_refine, candidate_list_refine, convex_weights_list_refine,
+         num_total_pos_refine, num_total_neg_refine, _) = cls_reg_targets_refine
+        num_total_samples_refine = (num_total_pos_refine + num_total_neg_refine if self.sampling
+                                    else num_total_pos_refine)
+        if torch.is_tensor(num_total_pos_refine) and isinstance(self.loss_bbox_init, ConvexGIoULoss) and \
+                isinstance(self.loss_bbox_refine, ConvexGIoULoss):
+            losses_pts_init = self._pts_loss_dense(self.loss_bbox_init, pts_coordinate_preds_init, rbbox_gt_list_init,
+                                                   convex_weights_list_init)
+            losses_pts_refine = self._pts_loss_dense(self.loss_bbox_refine, pts_coordinate_preds_refine,
+                                                     rbbox_gt_list_refine, convex_weights_list_refine)
+            losses_cls = [self._cls_loss(c, l, w, num_total_samples_refine)
+                          for c, l, w in zip(cls_scores, labels_list, label_weights_list)]
+        else:
+            losses_cls, losses_pts_init, losses_pts_refine = multi_apply(
+                self.loss_single, cls_scores, pts_coordinate_preds_init, pts_coordinate_preds_refine, labels_list,
+                label_weights_list, rbbox_gt_list_init, convex_weights_list_init, rbbox_gt_list_refine,
+                convex_weights_list_refine, self.point_strides, num_total_samples_refine=num_total_samples_refine)
+        return dict(loss_cls=losses_cls, loss_pts_init=losses_pts_init, loss_pts_refine=losses_pts_refine)
+
+    def _refine_proposals(self, center_list, pts_preds_init):
+        """per image and level (n_level, 18): centre + detached init offsets * stride, in the network's y-first order
+        as the reference hands them to the refine assigner (L706-720)"""
+        levels = []
+        for i_lvl, pred in enumerate(pts_preds_init):
+            shift = pred.detach().permute(0, 2, 3, 1) * self.point_strides[i_lvl]
+            center = center_list[0][i_lvl][:, :2].repeat(1, self.num_points)
+            levels.append(center + shift.reshape(shift.shape[0], -1, 2 * self.num_points))
+        return [[lvl[i_img] for lvl in levels] for i_img in range(len(center_list))]
+
+    # ------------------------------------------------------------------------------------------------------- inference
+    def get_bboxes(self, cls_scores, pts_preds_init, pts_preds_refine, img_metas, cfg=None, rescale=False,
+                   with_nms=True, **kwargs):
+        assert len(cls_scores) == len(pts_preds_refine)
+        num_levels = len(cls_scores)
+        featmap_sizes = [tuple(cls_scores[i].shape[-2:]) for i in range(num_levels)]
+        mlvl_priors = self.prior_generator.grid_priors(featmap_sizes, dtype=cls_scores[0].dtype,
+                                                       device=cls_scores[0].device)
+        result_list = []
+        for img_id, img_meta in enumerate(img_metas):
+            cls_score_list = [cls_scores[i][img_id].detach() for i in range(num_levels)]
+            point_pred_list = [pts_preds_refine[i][img_id].detach() for i in range(num_levels)]
+            result_list.append(self._get_bboxes_single(cls_score_list, point_pred_list, mlvl_priors, img_meta, cfg,
+                                                       rescale, with_nms, **kwargs))
+        return result_list
+
+    def _get_bboxes_single(self, cls_score_list, point_pred_list, mlvl_priors, img_meta, cfg, rescale=False,
+                           with_nms=True, **kwargs):
+        cfg = self.test_cfg if cfg is None else cfg
+        assert len(cls_score_list) == len(point_pred_list)
+        scale_factor = img_meta["scale_factor"]
+        mlvl_bboxes = []
+        mlvl_scores = []
+        for level_idx, (cls_score, points_pred, points) in enumerate(zip(cls_score_list, point_pred_list, mlvl_priors)):
+            assert cls_score.shape[-2:] == points_pred.shape[-2:]
+            cls_score = cls_score.permute(1, 2, 0).reshape(-1, self.cls_out_channels)
+            if self.use_sigmoid_cls:
+                scores = cls_score.sigmoid()
+            else:
+                scores = cls_score.softmax(-1)[:, :-1]
+            points_pred = points_pred.permute(1, 2, 0).reshape(-1, 2 * self.num_points)
+            nms_pre = cfg.get("nms_pre", -1)
+            if 0 < nms_pre < scores.shape[0]:
+                if self.use_sigmoid_cls:
+                    max_scores = scores.max(dim=1).values
+                else:
+                    max_scores = scores[:, 1:].max(dim=1).values
+                _, topk_inds = max_scores.topk(nms_pre)
+                points = points[topk_inds, :]
+                points_pred = points_pred[topk_inds, :]
+                scores = scores[topk_inds, :]
+            poly_pred = self.points2rotrect(points_pred, y_first=True)
+            bbox_pos_center = points[:, :2].repeat(1, 4)
+            polys = poly_pred * self.point_strides[level_idx] + bbox_pos_center
+            mlvl_bboxes.append(rectpoly2obb(polys))
+            mlvl_scores.append(scores)
+        mlvl_bboxes = torch.cat(mlvl_bboxes)
+        if rescale:
+            mlvl_bboxes = torch.cat([mlvl_bboxes[..., :4] / scale_factor, mlvl_bboxes[..., 4:]], dim=-1)
+        mlvl_scores = torch.cat(mlvl_scores)
+        if self.use_sigmoid_cls:
+            padding = mlvl_scores.new_zeros((mlvl_scores.shape[0], 1))
+            mlvl_scores = torch.cat([padding, mlvl_scores], dim=1)
+        if not with_nms:
+            raise NotImplementedError
+        det_bboxes, det_labels = multiclass_nms_rotated(mlvl_bboxes, mlvl_scores, cfg.score_thr, cfg.nms,
+                                                        cfg.max_per_img)
+        boxes = det_bboxes[:, :5]
+        scores = det_bboxes[:, 5]
+        return rotated_box_to_poly(boxes), scores, det_labels
+
+    def parse_targets(self, targets):
+        img_metas, gt_bboxes, gt_bboxes_ignore, gt_labels = [], [], [], []
+        for target in targets:
+            if self.training:
+                gt_bboxes.append(target["rboxes"])
+                gt_labels.append(target["labels"])
+                gt_bboxes_ignore.append(target["rboxes_ignore"])
+            img_metas.append(dict(img_shape=target["img_size"][::-1], scale_factor=target["scale_factor"],
+                                  pad_shape=target["pad_shape"]))
+        if not self.training:
+            return dict(img_metas=img_metas)
+        return dict(gt_bboxes=gt_bboxes, gt_labels=gt_labels, img_metas=img_metas, gt_bboxes_ignore=gt_bboxes_ignore)
+
+    def forward(self, feats, targets):
+        outs = multi_apply(self.forward_single, feats)
+        if self.training:
+            return self.loss(*outs, **self.parse_targets(targets))
+        return self.get_bboxes(*outs, **self.parse_targets(targets))
+
+    execute = forward
