@@ -190,6 +190,15 @@ REPPOINTS_SIGNATURES = {
     "jdet_convex_giou_loss": (_i, [_p, _p, _p, _p, _l, _p, _p, _p]),
 }
 
+# include/jdet_hip_h2rbox.h (csrc/rotate_crop.hip, csrc/h2rbox_aug_loss.hip; same library, a table of its own for the
+# reason ATSS_SIGNATURES has one; tests/test_h2rbox_cpu.py checks it against the header and the exports)
+H2RBOX_SIGNATURES = {
+    "jdet_rotate_crop": (_i, [_p, _i, _i, _i, _i, _i, _i, _f, _f, _i, _p, _p]),
+    "jdet_h2rbox_aug_loss_forward": (_i, [_p, _i, _p, _p, _p, _p, _p, _i, _i, _f, _f, _f, _i, _i, _f, _f, _f, _p, _p, _p]),
+    "jdet_h2rbox_aug_loss_backward": (_i, [_p, _i, _p, _p, _p, _p, _p, _i, _i, _f, _f, _f, _i, _i, _f, _f, _f, _p, _p, _p,
+                                           _p, _p, _p, _p, _p]),
+}
+
 _lib = None
 
 # Hull-point ordering inside the rotated IoU: 0 = the reference's CPU path (std::sort,
@@ -221,7 +230,8 @@ def lib():
         # streams and allocations.
         l = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in list(SIGNATURES.items()) + list(ATSS_SIGNATURES.items()) + list(ROWS_SIGNATURES.items()) + \
-                list(ROWS_FWD_SIGNATURES.items()) + list(FCOS_SIGNATURES.items()) + list(REPPOINTS_SIGNATURES.items()):
+                list(ROWS_FWD_SIGNATURES.items()) + list(FCOS_SIGNATURES.items()) + list(REPPOINTS_SIGNATURES.items()) + \
+                list(H2RBOX_SIGNATURES.items()):
             fn = getattr(l, name)  # AttributeError here == ABI drift: fail loudly
             fn.restype = res
             fn.argtypes = args

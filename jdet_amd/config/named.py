@@ -197,6 +197,34 @@ FCOS_CFG = dict(
     scheduler=dict(type="StepLR", warmup="linear", warmup_iters=500, warmup_ratio=1.0 / 3, milestones=[8, 11]))
 
 
+H2RBOX_CFG = dict(
+    # configs/h2rbox/h2rbox_obb_r50_adamw_fpn_1x_dota.py: model L2-52, optimizer L126-131, scheduler L133-138
+    # (tests/golden/configs/h2rbox_obb_r50_adamw_fpn_1x_dota.yaml holds them as `Config` reads them).  FCOS trained from
+    # HORIZONTAL boxes: two views of every batch (jdet_rotate_crop), the horizontal IoU loss on the circumscribed boxes
+    # and the view-consistency loss (jdet_h2rbox_aug_loss_*); rect_classes are the 0-based labels of inference.
+    model=dict(
+        type="H2RBox", crop_size=(1024, 1024), padding="reflection",
+        backbone=dict(type="Resnet50", frozen_stages=1, norm_eval=True,
+                      return_stages=["layer1", "layer2", "layer3", "layer4"], pretrained=True),
+        neck=dict(type="FPN", in_channels=[256, 512, 1024, 2048], out_channels=256, start_level=1,
+                  add_extra_convs="on_output", num_outs=5, relu_before_extra_convs=True),
+        roi_heads=dict(
+            type="H2RBoxHead", num_classes=15, in_channels=256, stacked_convs=4, feat_channels=256,
+            strides=[8, 16, 32, 64, 128], scale_theta=True, norm_on_bbox=True, crop_size=(1024, 1024),
+            rect_classes=[9, 11],
+            loss_cls=dict(type="FocalLoss", gamma=2.0, alpha=0.25, loss_weight=1.0),
+            loss_bbox=dict(type="IoULoss", loss_weight=1.0),
+            loss_centerness=dict(type="CrossEntropyLoss", use_bce=True, loss_weight=1.0),
+            loss_bbox_aug=dict(type="H2RBoxLoss", loss_weight=0.4,
+                               center_loss_cfg=dict(type="L1Loss", loss_weight=0.0),
+                               shape_loss_cfg=dict(type="IoULoss", loss_weight=1.0),
+                               angle_loss_cfg=dict(type="L1Loss", loss_weight=1.0)),
+            test_cfg=dict(centerness_factor=0.5, nms_pre=1000, min_bbox_size=0, score_thr=0.05,
+                          nms=dict(type="obb_nms", iou_thr=0.1), max_per_img=2000))),
+    optimizer=dict(type="AdamW", lr=0.0001, betas=(0.9, 0.999), weight_decay=0.05),
+    scheduler=dict(type="StepLR", warmup="linear", warmup_iters=500, warmup_ratio=1.0 / 3, milestones=[8, 11]))
+
+
 REPPOINTS_CFG = dict(
     # configs/rotated_reppoints_obb_r50_fpn_1x_dota.py: model L2-65, optimizer L138-146, scheduler L148-153
     # (tests/golden/configs/rotated_reppoints_obb_r50_fpn_1x_dota.yaml holds them as `Config` reads them).  Anchor-free:

@@ -23,7 +23,7 @@ from torch.utils.data import DataLoader, Dataset
 
 from jdet_amd.utils.registry import DATASETS
 
-from .np_boxes import rotated_box_to_bbox_np, rotated_box_to_poly_np
+from .np_boxes import poly_to_rotated_box_np, rotated_box_to_bbox_np, rotated_box_to_poly_np
 from .transforms import Compose
 
 DOTA1_CLASSES = ["plane", "baseball-diamond", "bridge", "ground-track-field", "small-vehicle", "large-vehicle", "ship",
@@ -211,6 +211,36 @@ class DOTADataset(CustomDataset):
             with open(os.path.join(path, "val.pkl"), "wb") as f:
                 pickle.dump(results, f)
         return evaluate_dota(results, self.CLASSES, iou_matrix_fn or device_iou_matrix)
+
+
+def rotated_box_to_hbbox_np(rotated_boxes):
+    """(n, 5) rotated boxes -> (n, 5) their circumscribed HORIZONTAL boxes written as rotated boxes (data/h2rbox_data.py:
+    L68-78): the corners' extremes, as the polygon (xmin, ymin) (xmin, ymax) (xmax, ymax) (xmax, ymin), through
+    poly_to_rotated_box_np -- so a box wider than tall gets angle 0 and a taller one (w, h) = (height, width) with
+    angle pi / 2.  The weak supervision of H2RBox: the angle of the annotation never reaches the detector."""
+    rotated_boxes = np.asarray(rotated_boxes)
+    if rotated_boxes.shape[0] == 0:
+        return np.zeros((0, 5), np.float32)     # (the reference returns a pair of empty arrays here: not a box array)
+    polys = rotated_box_to_poly_np(rotated_boxes)
+    xmin = polys[:, ::2].min(1, keepdims=True)
+    ymin = polys[:, 1::2].min(1, keepdims=True)
+    xmax = polys[:, ::2].max(1, keepdims=True)
+    ymax = polys[:, 1::2].max(1, keepdims=True)
+    return poly_to_rotated_box_np(np.concatenate([xmin, ymin, xmin, ymax, xmax, ymax, xmax, ymin], axis=1))
+
+
+@DATASETS.register_module()
+class DOTAWSOODDataset(DOTADataset):
+    """DOTA with the rotated annotations replaced by their horizontal boxes (data/h2rbox_data.py:L27-113): `rboxes` is
+    what H2RBox trains from, `hboxes` / `polys` keep the original geometry for evaluation.  The record on disk is left
+    alone (the reference overwrites anno['bboxes'] in place)."""
+
+    rotated_box_to_hbbox_np = staticmethod(rotated_box_to_hbbox_np)
+
+    def _read_ann_info(self, idx):
+        image, ann = super()._read_ann_info(idx)
+        ann["rboxes"] = self.rotated_box_to_hbbox_np(ann["rboxes"]).astype(np.float32)
+        return image, ann
 
 
 @DATASETS.register_module()

@@ -5,3 +5,5 @@ from .gaussian_dist_loss import GDLoss, GDLoss_v1  # noqa: F401
 from .kf_iou_loss import KFLoss  # noqa: F401
 from .poly_iou_loss import PolyIoULoss, poly_iou_loss  # noqa: F401
 from .convex_giou_loss import ConvexGIoULoss  # noqa: F401
+from .iou_loss import IoULoss, iou_loss  # noqa: F401
+from .h2rbox_loss import H2RBoxLoss  # noqa: F401

@@ -4,3 +4,4 @@ from .rotated_retinanet import RotatedRetinaNet  # noqa: F401
 from .roi_transformer import RoITransformer  # noqa: F401
 from .gliding_vertex import GlidingVertex  # noqa: F401
 from .fcos import FCOS, SingleStageDetector  # noqa: F401
+from .h2rbox import H2RBox  # noqa: F401

@@ -10,4 +10,5 @@ from .fasterrcnn_head import AnchorHead, FasterrcnnHead  # noqa: F401
 from .gliding_rpn_head import GlidingRPNHead  # noqa: F401
 from .gliding_head import GlidingHead  # noqa: F401
 from .fcos_head import FCOSHead  # noqa: F401
+from .h2rbox_head import H2RBoxHead  # noqa: F401
 from .rotated_reppoints_head import MlvlPointGenerator, RotatedRepPointsHead  # noqa: F401

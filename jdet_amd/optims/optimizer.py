@@ -1,4 +1,4 @@
-"""SGD with gradient clipping.  Mirrors python/jdet/optims/optimizer.py:L8-36: `step(loss)` =
+"""SGD and AdamW with gradient clipping.  Mirrors python/jdet/optims/optimizer.py:L8-36: `step(loss)` =
 backward -> (data-parallel gradient all-reduce, inside Jittor there; DDP's bucketed RCCL all-reduce
 overlapped with backward here) -> clip_grad_norm(**grad_clip) -> momentum SGD with weight decay."""
 import os
@@ -13,8 +13,34 @@ from jdet_amd.utils.registry import OPTIMS
 FUSED = os.environ.get("JDET_FUSED_SGD", "1") == "1"
 
 
+class _RunnerInterface:
+    """what the runner and the schedulers ask of an optimiser besides `step(loss)` (optims/optimizer.py:L8-36 of the
+    reference), shared by SGD and AdamW"""
+
+    def _backward(self, loss):
+        if loss is not None:
+            self.zero_grad(set_to_none=True)
+            loss.backward()
+
+    def _clip(self):
+        """clip_grad_norm_(**grad_clip) over the parameters that have a gradient"""
+        params = [p for g in self.param_groups for p in g["params"] if p.grad is not None]
+        torch.nn.utils.clip_grad_norm_(params, max_norm=self.grad_clip["max_norm"],
+                                       norm_type=float(self.grad_clip.get("norm_type", 2)), foreach=True)
+
+    def cur_lr(self):
+        return self.param_groups[0].get("lr", self.lr)
+
+    def parameters(self):
+        return self.state_dict()
+
+    def load_parameters(self, data):
+        if isinstance(data, dict) and "param_groups" in data:
+            self.load_state_dict(data)
+
+
 @OPTIMS.register_module()
-class SGD(torch.optim.SGD):
+class SGD(_RunnerInterface, torch.optim.SGD):
     def __init__(self, params, lr, momentum=0, weight_decay=0, dampening=0, nesterov=False, grad_clip=None):
         params = [p for p in params if p.requires_grad]
         self.fused_step = bool(FUSED and params and all(p.is_cuda and p.dtype == torch.float32 for p in params))
@@ -73,12 +99,23 @@ class SGD(torch.optim.SGD):
                 ok = False
         return ok
 
-    def cur_lr(self):
-        return self.param_groups[0].get("lr", self.lr)
 
-    def parameters(self):
-        return self.state_dict()
+@OPTIMS.register_module()
+class AdamW(_RunnerInterface, torch.optim.AdamW):
+    """optims/optimizer.py:L75-77 of the reference (Jittor's AdamW under the same `step(loss)` interface): decoupled
+    weight decay.  Device fp32 parameters take torch's fused multi-tensor kernel, everything else the foreach form;
+    `grad_clip` is clip_grad_norm_ before the update, as for SGD."""
 
-    def load_parameters(self, data):
-        if isinstance(data, dict) and "param_groups" in data:
-            self.load_state_dict(data)
+    def __init__(self, params, lr, eps=1e-8, betas=(0.9, 0.999), weight_decay=0, grad_clip=None):
+        params = [p for p in params if p.requires_grad]
+        fused = bool(FUSED and params and all(p.is_cuda and p.dtype == torch.float32 for p in params))
+        kind = dict(fused=True) if fused else dict(foreach=True)
+        super().__init__(params, lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, **kind)
+        self.grad_clip = dict(grad_clip) if grad_clip is not None else None
+        self.lr = lr
+
+    def step(self, loss=None):
+        self._backward(loss)
+        if self.grad_clip is not None:
+            self._clip()
+        super().step()
