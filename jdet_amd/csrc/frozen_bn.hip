@@ -13,7 +13,7 @@
 //             (a thread keeps the same 4 channels for its whole grid-stride loop), are combined per
 //             workgroup through LDS and finished by a second tiny launch -- deterministic, no atomics.
 // Tensors are [P][C] with P = N*H*W, C % 4 == 0, every access a float4.
-#include "common.h"
+#include "reduce.h"
 
 namespace {
 
@@ -118,32 +118,15 @@ __global__ __launch_bounds__(1024) void frozen_bn_bwd_kernel(const v4f* __restri
     if (AFFINE) xx = x[i];
     one(i, d, yy, xx);
   }
-  if (AFFINE) {
-    float* mine = s_red + (size_t)threadIdx.x * 8;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      mine[k] = sg[k];
-      mine[4 + k] = sgx[k];
-    }
-    __syncthreads();
-    // threads 0..cpt-1 own one channel quad each; the others of the workgroup with the same quad sit at
-    // threadIdx + m*cpt (blockDim is a multiple of cpt)
-    if ((int)threadIdx.x < cpt) {
-      float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-      for (int t = threadIdx.x; t < (int)blockDim.x; t += cpt)
-#pragma unroll
-        for (int k = 0; k < 8; k++) acc[k] += s_red[(size_t)t * 8 + k];
-      // quad of thread t in this workgroup: (blockIdx*blockDim + t) % cpt == t because blockDim % cpt == 0
-      float* out = partial + (size_t)blockIdx.x * 2 * cpt * 4;
-#pragma unroll
-      for (int k = 0; k < 4; k++) {
-        out[threadIdx.x * 4 + k] = acc[k];                 // dbeta partials
-        out[cpt * 4 + threadIdx.x * 4 + k] = acc[4 + k];   // dgamma partials
-      }
-    }
+  if (AFFINE) {   // dbeta and dgamma partials of this workgroup: one row
+    const float sums[8] = {sg[0], sg[1], sg[2], sg[3], sgx[0], sgx[1], sgx[2], sgx[3]};
+    jdet_quad_partials<8>(s_red, sums, cpt, partial + (size_t)blockIdx.x * 2 * cpt * 4);
   }
 }
 
+// frozen_bn_bwd_kernel above and bn_out_bwd_kernel below stay two kernels on purpose: they share the epilogue
+// (jdet_quad_partials) and the launch geometry only; one body for both would put the loads and factors of either into
+// the other's register budget.
 // Backward of y = relu(bn(c) + idn) FROM ITS OUTPUT: the fused convolution (conv_bn.hip) never stores c, and wherever
 // y > 0 the normalised input is recoverable as xhat = (y - idn - beta) / gamma.  One pass: reads dy, y (, idn); writes
 // dc = dy * [y > 0] * a; per-channel partial sums of g = dy * [y > 0] and g * (y - idn - beta) -- the second stage
@@ -192,28 +175,13 @@ __global__ __launch_bounds__(1024) void bn_out_bwd_kernel(const v4f* __restrict_
     one(i, d, yy, rr);
   }
   if (AFFINE) {
-    float* mine = s_red + (size_t)threadIdx.x * 8;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      mine[k] = sg[k];
-      mine[4 + k] = sgx[k];
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < cpt) {
-      float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-      for (int t = threadIdx.x; t < (int)blockDim.x; t += cpt)
-#pragma unroll
-        for (int k = 0; k < 8; k++) acc[k] += s_red[(size_t)t * 8 + k];
-      float* out = partial + (size_t)blockIdx.x * 2 * cpt * 4;
-#pragma unroll
-      for (int k = 0; k < 4; k++) {
-        out[threadIdx.x * 4 + k] = acc[k];
-        out[cpt * 4 + threadIdx.x * 4 + k] = acc[4 + k];
-      }
-    }
+    const float sums[8] = {sg[0], sg[1], sg[2], sg[3], sgx[0], sgx[1], sgx[2], sgx[3]};
+    jdet_quad_partials<8>(s_red, sums, cpt, partial + (size_t)blockIdx.x * 2 * cpt * 4);
   }
 }
 
+// bn_sums_finish_kernel is NOT sums_finish_kernel (further down) with jobs: four rows in flight in a loop here, eight
+// in a tree there -- two orders of addition, and merging them would move gradient bits.
 // Second stage for up to 4 BatchNorm layers in ONE launch (a bottleneck's three or four): job j sums its partial rows
 // [rows][2][C] in a fixed order; grad_beta = sum of the first halves, grad_gamma = (sum of the second halves) / gamma.
 // gamma == 0 leaves xhat unrecoverable from the activation: the quotient is then inf / NaN on purpose (a silent 0 would
@@ -303,19 +271,8 @@ __global__ __launch_bounds__(1024) void bias_act_bwd_kernel(const v4f* __restric
     }
     sg += d;
   }
-  float* mine = s_red + (size_t)threadIdx.x * 4;
-#pragma unroll
-  for (int k = 0; k < 4; k++) mine[k] = sg[k];
-  __syncthreads();
-  if ((int)threadIdx.x < cpt) {     // threads t, t + cpt, ... of the workgroup hold the same channel quad
-    float acc[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int t = threadIdx.x; t < (int)blockDim.x; t += cpt)
-#pragma unroll
-      for (int k = 0; k < 4; k++) acc[k] += s_red[(size_t)t * 4 + k];
-    float* out = partial + (size_t)blockIdx.x * 2 * cpt * 4;      // row layout of sums_finish_kernel (dbeta half)
-#pragma unroll
-    for (int k = 0; k < 4; k++) out[threadIdx.x * 4 + k] = acc[k];
-  }
+  const float sums[4] = {sg[0], sg[1], sg[2], sg[3]};
+  jdet_quad_partials<4>(s_red, sums, cpt, partial + (size_t)blockIdx.x * 2 * cpt * 4);   // the dbeta half of a row
 }
 
 // Per-channel sum of channels-last rows (P, C) for ANY channel count up to 256 (the classification / regression
@@ -413,6 +370,26 @@ int geometry(long P, int C, int max_grid, Geo& g) {
 constexpr int kFwdGrid = 4096;
 constexpr int kBwdGrid = 512;    // rows of the partial-sum workspace
 
+// Geometry of the backward entries.  Those that write partial rows (`sums`) want 1024-thread workgroups -- a multiple of
+// the channel-quad count, as the LDS combine needs, so only where 1024 % cpt == 0 -- and at most 256 of them, so that
+// sums_finish_kernel has every partial row of a thread in flight at once.  Two behaviours exist and both are recorded
+// by tests/test_gpu_bn_sums.py:
+//   cap_always = false (the BN entries): block and cap change together, otherwise geometry()'s 512 rows stay
+//                                        (C = 1536: 384-thread workgroups, 512 rows)
+//   cap_always = true  (the bias entry): at most 256 workgroups whatever the block (C = 1536: 256 rows)
+int bwd_geometry(long P, int C, bool sums, bool cap_always, Geo& g) {
+  int e = geometry(P, C, kBwdGrid, g);
+  if (e) return e;
+  const bool wide = sums && 1024 % g.cpt == 0;
+  if (wide) g.block = 1024;
+  if (wide || cap_always) {
+    const size_t n4 = (size_t)P * g.cpt;
+    const long want = (long)((n4 + (size_t)g.block * 4 - 1) / ((size_t)g.block * 4));
+    g.grid = (int)(want < 1 ? 1 : (want > 256 ? 256 : want));
+  }
+  return JDET_OK;
+}
+
 }  // namespace
 
 JDET_API int jdet_frozen_bn_act_forward(const float* x_nhwc, const float* residual_nhwc, long P, int C,
@@ -452,10 +429,10 @@ JDET_API int jdet_frozen_bn_act_backward(const float* grad_y_nhwc, const float* 
                                          float* grad_residual_nhwc, float* grad_weight, float* grad_bias,
                                          void* workspace, size_t workspace_bytes, jdet_stream_t stream) {
   Geo g;
-  int e = geometry(P, C, kBwdGrid, g);
+  const bool affine = grad_weight != nullptr || grad_bias != nullptr;
+  int e = bwd_geometry(P, C, affine, false, g);
   if (e) return e;
   if (P == 0) return JDET_OK;
-  const bool affine = grad_weight != nullptr || grad_bias != nullptr;
   if (!grad_y_nhwc || !grad_x_nhwc || !running_mean || !running_var || (relu && !y_nhwc) || (affine && !x_nhwc))
     return JDET_E_BADARG;
   if (affine && (!workspace || workspace_bytes < jdet_frozen_bn_act_backward_workspace(P, C))) return JDET_E_WORKSPACE;
@@ -468,13 +445,6 @@ JDET_API int jdet_frozen_bn_act_backward(const float* grad_y_nhwc, const float* 
   v4f* dx = (v4f*)grad_x_nhwc;
   v4f* dr = (v4f*)grad_residual_nhwc;
   float* part = (float*)workspace;
-  if (affine && 1024 % g.cpt == 0) {
-    // affine pass: 1024-thread workgroups (a multiple of the channel-quad count, as the LDS combine needs) and at
-    // most 256 of them, so that the second stage has every partial row of a thread in flight at once
-    g.block = 1024;
-    long want = (long)((n4 + (size_t)g.block * 4 - 1) / ((size_t)g.block * 4));
-    g.grid = (int)(want < 1 ? 1 : (want > 256 ? 256 : want));
-  }
   const size_t lds = affine ? sizeof(float) * 8 * (size_t)g.block : 0;
 #define JDET_BN_BWD(RELU, RES, AFF)                                                                            \
   hipLaunchKernelGGL((frozen_bn_bwd_kernel<RELU, RES, AFF>), dim3(g.grid), dim3(g.block), lds, st, dy, y, x, dx, dr, \
@@ -504,19 +474,14 @@ JDET_API int jdet_bias_act_backward(const float* grad_y_nhwc, const float* y_nhw
                                     float* grad_pre_nhwc, float* grad_bias, void* workspace, size_t workspace_bytes,
                                     jdet_stream_t stream) {
   Geo g;
-  int e = geometry(P, C, kBwdGrid, g);
+  int e = bwd_geometry(P, C, true, true, g);
   if (e) return e;
   if (!grad_bias) return JDET_E_BADARG;
   hipStream_t st = (hipStream_t)stream;
   if (P == 0) return jdet_zero_async(grad_bias, sizeof(float) * (size_t)C, st);
   if (!grad_y_nhwc || (relu && (!y_nhwc || !grad_pre_nhwc))) return JDET_E_BADARG;
   if (!workspace || workspace_bytes < jdet_frozen_bn_act_backward_workspace(P, C)) return JDET_E_WORKSPACE;
-  // 1024-thread workgroups (a multiple of the channel-quad count, as the LDS combine needs) and at most 256 of them:
-  // a quarter of the partial rows of the BN kernels' geometry for the second stage to read
-  if (1024 % g.cpt == 0) g.block = 1024;
   const size_t n4 = (size_t)P * g.cpt;
-  long want = (long)((n4 + (size_t)g.block * 4 - 1) / ((size_t)g.block * 4));
-  g.grid = (int)(want < 1 ? 1 : (want > 256 ? 256 : want));
   const size_t lds = sizeof(float) * 4 * (size_t)g.block;
   float* part = (float*)workspace;
   if (relu)
@@ -531,26 +496,10 @@ JDET_API int jdet_bias_act_backward(const float* grad_y_nhwc, const float* y_nhw
   return jdet_launch_status();
 }
 
-namespace {
-// launch geometry of the output-based backward with sums: 1024-thread workgroups where the channel-quad count divides
-// 1024 (as the LDS combine needs), at most 256 of them
-int out_bwd_geometry(long P, int C, bool affine, Geo& g) {
-  int e = geometry(P, C, kBwdGrid, g);
-  if (e) return e;
-  if (affine && 1024 % g.cpt == 0) {
-    const size_t n4 = (size_t)P * g.cpt;
-    g.block = 1024;
-    long want = (long)((n4 + (size_t)g.block * 4 - 1) / ((size_t)g.block * 4));
-    g.grid = (int)(want < 1 ? 1 : (want > 256 ? 256 : want));
-  }
-  return JDET_OK;
-}
-}  // namespace
-
 /* rows of partial sums ([rows][2][C] floats) jdet_bn_act_backward_from_output writes for a (P, C) tensor; 0 = unsupported */
 JDET_API size_t jdet_bn_act_backward_from_output_rows(long P, int C) {
   Geo g;
-  if (out_bwd_geometry(P, C, true, g) || P == 0) return 0;
+  if (bwd_geometry(P, C, true, false, g) || P == 0) return 0;
   return (size_t)g.grid;
 }
 
@@ -568,7 +517,7 @@ JDET_API int jdet_bn_act_backward_from_output(const float* grad_y_nhwc, const fl
                                               jdet_stream_t stream) {
   Geo g;
   const bool affine = sums != nullptr;
-  int e = out_bwd_geometry(P, C, affine, g);
+  int e = bwd_geometry(P, C, affine, false, g);
   if (e) return e;
   if (P == 0) return JDET_OK;
   if (!grad_y_nhwc || !y_nhwc || !grad_c_nhwc || !running_mean || !running_var) return JDET_E_BADARG;

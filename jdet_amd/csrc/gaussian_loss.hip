@@ -11,6 +11,7 @@
 // the row when weight.mean(-1) > 0 (the weight is a mask only, as in the reference).  Per-workgroup partials, one
 // finishing workgroup: (sum / *avg_factor) * loss_weight.  Deterministic, no atomics, no allocation, no host sync.
 #include "box_codec.h"
+#include "reduce.h"
 
 namespace {
 
@@ -253,21 +254,6 @@ __device__ D5 kfiou(const D5* dp, const float* dt, const Gauss& p, const Gauss& 
   return dclamp_min(xy_loss + kf_loss, 0.f);
 }
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
-struct Blocked {
-  long rows_per_block;
-  long block_stride;
-};
-__device__ __forceinline__ long blocked_row(const Blocked& b, long r) {
-  const long blk = r / b.rows_per_block;
-  return blk * b.block_stride + (r - blk * b.rows_per_block);
-}
-
 // one thread per row; rows with weight.mean(-1) <= 0 contribute 0 and a zero gradient
 __global__ __launch_bounds__(256) void gaussian_loss_kernel(const float* __restrict__ pred,
                                                             const float* __restrict__ target, Blocked tb,
@@ -342,28 +328,9 @@ __global__ __launch_bounds__(256) void gaussian_loss_kernel(const float* __restr
 #pragma unroll
     for (int k = 0; k < 5; k++) grad[r * 5 + k] = g[k];
   }
-  acc = wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) partial[blockIdx.x] = (s_part[0] + s_part[1]) + (s_part[2] + s_part[3]);
+  const float sum = jdet_block_sum4(acc, s_part);
+  if (threadIdx.x == 0) partial[blockIdx.x] = sum;
 }
-
-__global__ __launch_bounds__(256) void gaussian_finish_kernel(const float* __restrict__ partial, int n,
-                                                              const float* __restrict__ avg_factor, float loss_weight,
-                                                              float* __restrict__ out) {
-  __shared__ float s_part[4];
-  float acc = 0.f;
-  for (int i = threadIdx.x; i < n; i += 256) acc += partial[i];
-  acc = wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const float total = (s_part[0] + s_part[1]) + (s_part[2] + s_part[3]);
-    out[0] = (total / avg_factor[0]) * loss_weight;
-  }
-}
-
-constexpr int kGaussGrid = 1024;   // = the focal-loss workspace (jdet_sigmoid_focal_loss_workspace: 1024 floats)
 
 }  // namespace
 
@@ -383,7 +350,7 @@ JDET_API int jdet_gaussian_loss_level(const float* pred, const float* target, lo
   if (target_rows_per_block <= 0 || target_block_stride < 0 ||
       (weight && (weight_rows_per_block <= 0 || weight_block_stride < 0)))
     return JDET_E_BADARG;
-  if (workspace_bytes < sizeof(float) * kGaussGrid) return JDET_E_WORKSPACE;
+  if (workspace_bytes < jdet_sigmoid_focal_loss_workspace()) return JDET_E_WORKSPACE;
   Vec5 m, s;
   for (int k = 0; k < 5; k++) {
     m.v[k] = q.means[k];
@@ -391,16 +358,12 @@ JDET_API int jdet_gaussian_loss_level(const float* pred, const float* target, lo
   }
   const float max_ratio = (q.decode_pred || q.decode_target) ? fabsf(logf(q.wh_ratio_clip)) : 0.f;
   hipStream_t st = (hipStream_t)stream;
-  int grid = jdet_cdiv(rows, 256);
-  if (grid > kGaussGrid) grid = kGaussGrid;
+  const int grid = jdet_loss_grid(rows, 256);
   hipLaunchKernelGGL(gaussian_loss_kernel, dim3(grid), dim3(256), 0, st, pred, target,
                      Blocked{target_rows_per_block, target_block_stride}, weight,
                      Blocked{weight ? weight_rows_per_block : 1, weight ? weight_block_stride : 0},
                      (q.decode_pred || q.decode_target) ? anchors : nullptr, anchor_rows > 0 ? anchor_rows : 1, rows,
                      q, m, s, max_ratio, grad_pred, (float*)workspace);
-  int e = jdet_launch_status();
-  if (e) return e;
-  hipLaunchKernelGGL(gaussian_finish_kernel, dim3(1), dim3(256), 0, st, (const float*)workspace, grid, avg_factor,
-                     loss_weight, loss);
-  return jdet_launch_status();
+  if (int e = jdet_launch_status()) return e;
+  return jdet_sum_partials<true>((const float*)workspace, grid, avg_factor, loss_weight, loss, st);
 }

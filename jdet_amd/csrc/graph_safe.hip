@@ -9,7 +9,7 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "common.h"
+#include "reduce.h"
 
 namespace {
 
@@ -28,19 +28,15 @@ __global__ __launch_bounds__(256) void sumsq_partial_kernel(const float* __restr
   }
   if (blockIdx.x == 0)
     for (size_t i = (n4 << 2) + threadIdx.x; i < n; i += 256) acc += (double)(x[i] * x[i]);
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) acc += __shfl_xor(acc, m, 64);
-  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) partial[blockIdx.x] = (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
+  const double sum = jdet_block_sum4(acc, s_red);
+  if (threadIdx.x == 0) partial[blockIdx.x] = sum;
 }
 
 __global__ __launch_bounds__(1024) void sumsq_finish_kernel(const double* __restrict__ partial, int nblocks,
                                                             float* __restrict__ out, int take_sqrt) {
   __shared__ double s_red[16];
   double acc = threadIdx.x < nblocks ? partial[threadIdx.x] : 0.0;
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) acc += __shfl_xor(acc, m, 64);
+  acc = jdet_wave_sum(acc);      // 16 waves: their sums are added one by one below, not jdet_block_sum4's tree
   if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = acc;
   __syncthreads();
   if (threadIdx.x == 0) {

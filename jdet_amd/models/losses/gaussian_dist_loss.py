@@ -13,6 +13,8 @@ from torch import nn
 
 from jdet_amd.utils.registry import LOSSES
 
+from ._level import blocked_rows, loss_workspace, scale_unit_grad
+
 
 def reduce_loss(loss, reduction="mean", avg_factor=None):
     if avg_factor is None:
@@ -202,7 +204,6 @@ class GaussianLevel(torch.autograd.Function):
     @staticmethod
     def forward(ctx, deltas, target, weight, anchors, params, avg_factor, loss_weight):
         from jdet_amd import _lib as L
-        from .focal_loss import blocked_rows
         p = deltas.contiguous()
         rows = p.shape[0]
         tb = blocked_rows(target, 5)
@@ -210,8 +211,7 @@ class GaussianLevel(torch.autograd.Function):
         anc = anchors.contiguous() if anchors is not None else None
         out = torch.empty((), dtype=torch.float32, device=p.device)
         grad = torch.empty_like(p)
-        wsb = L.lib().jdet_sigmoid_focal_loss_workspace()
-        ws = torch.empty((wsb,), dtype=torch.uint8, device=p.device)
+        ws, wsb = loss_workspace(p.device)
         L.check(L.lib().jdet_gaussian_loss_level(
             L.ptr(p), L.ptr(target), tb[0], tb[1], L.ptr(weight) if weight is not None else None, wb[0], wb[1],
             L.ptr(anc), anc.shape[0] if anc is not None else 0, rows, params, L.ptr(avg_factor), float(loss_weight),
@@ -222,13 +222,8 @@ class GaussianLevel(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out):
-        from jdet_amd import _lib as L
         grad, avg = ctx.saved_tensors
-        go = grad_out.to(torch.float32).contiguous()
-        out = torch.empty_like(grad)
-        L.check(L.lib().jdet_loss_grad_scale(L.ptr(grad), grad.numel(), L.ptr(go), L.ptr(avg), ctx.loss_weight,
-                                             L.ptr(out), L.stream_ptr(grad)), "jdet_loss_grad_scale")
-        return out, None, None, None, None, None, None
+        return (scale_unit_grad(grad, grad_out, avg, ctx.loss_weight),) + (None,) * 6
 
 
 def level_params(kind, fun, coder=None, decode_pred=False, decode_target=False, tau=0.0, alpha=1.0, normalize=True,
@@ -250,7 +245,6 @@ def level_params(kind, fun, coder=None, decode_pred=False, decode_target=False, 
 
 def _node_ok(deltas, target, weight, anchors, avg_factor, reduction, coder, decoding):
     from jdet_amd.models.boxes.coder import DeltaXYWHABBoxCoder
-    from .focal_loss import blocked_rows
     if reduction not in ("mean", "sum") or (reduction == "mean" and avg_factor is None):
         return False
     if not (deltas.is_cuda and deltas.dtype == torch.float32 and deltas.dim() == 2 and deltas.shape[1] == 5 and

@@ -4,6 +4,9 @@ from torch import nn
 
 from jdet_amd.utils.registry import LOSSES
 
+from . import _level
+from ._level import blocked_rows, device_scalar, loss_workspace, scale_unit_grad
+
 
 def smooth_l1_loss(pred, target, weight=None, beta=1.0, avg_factor=None, reduction="mean"):
     diff = torch.abs(pred - target)
@@ -55,8 +58,7 @@ class _FusedSmoothL1(torch.autograd.Function):
             w = w.contiguous()
         out = torch.empty((), dtype=torch.float32, device=p.device)
         grad = torch.empty_like(p)
-        wsb = L.lib().jdet_sigmoid_focal_loss_workspace()
-        ws = torch.empty((wsb,), dtype=torch.uint8, device=p.device)
+        ws, wsb = loss_workspace(p.device)
         L.check(L.lib().jdet_smooth_l1_loss(L.ptr(p), L.ptr(t), L.ptr(w), p.numel(), float(beta), out.data_ptr(),
                                             L.ptr(grad), L.ptr(ws), wsb, L.stream_ptr(p)), "jdet_smooth_l1_loss")
         ctx.save_for_backward(grad)
@@ -75,15 +77,13 @@ class _SmoothL1Level(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pred, target, weight, beta, avg_factor, loss_weight):
         from jdet_amd import _lib as L
-        from .focal_loss import blocked_rows
         p = pred.contiguous()
         rows, E = p.shape
         tb = blocked_rows(target, E)
         wb = blocked_rows(weight, E) if weight is not None else (1, 0)
         out = torch.empty((), dtype=torch.float32, device=p.device)
         grad = torch.empty_like(p)
-        wsb = L.lib().jdet_sigmoid_focal_loss_workspace()
-        ws = torch.empty((wsb,), dtype=torch.uint8, device=p.device)
+        ws, wsb = loss_workspace(p.device)
         L.check(L.lib().jdet_smooth_l1_loss_level(
             L.ptr(p), L.ptr(target), tb[0], tb[1], L.ptr(weight) if weight is not None else None, wb[0], wb[1], rows, E,
             float(beta), L.ptr(avg_factor), float(loss_weight), out.data_ptr(), L.ptr(grad), L.ptr(ws), wsb,
@@ -94,18 +94,12 @@ class _SmoothL1Level(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out):
-        from jdet_amd import _lib as L
         grad, avg = ctx.saved_tensors
-        go = grad_out.to(torch.float32).contiguous()
-        out = torch.empty_like(grad)
-        L.check(L.lib().jdet_loss_grad_scale(L.ptr(grad), grad.numel(), L.ptr(go), L.ptr(avg), ctx.loss_weight,
-                                             L.ptr(out), L.stream_ptr(grad)), "jdet_loss_grad_scale")
-        return out, None, None, None, None, None
+        return (scale_unit_grad(grad, grad_out, avg, ctx.loss_weight),) + (None,) * 5
 
 
 def _level_ok(pred, target, weight, avg_factor):
-    from .focal_loss import LEVEL_NODES, blocked_rows, device_scalar
-    if not (LEVEL_NODES and pred.is_cuda and pred.dtype == torch.float32 and pred.dim() == 2 and pred.numel() > 0 and
+    if not (_level.LEVEL_NODES and pred.is_cuda and pred.dtype == torch.float32 and pred.dim() == 2 and pred.numel() > 0 and
             not torch.is_autocast_enabled() and device_scalar(avg_factor) and not target.requires_grad):
         return False
     E = pred.shape[1]

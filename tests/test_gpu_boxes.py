@@ -256,6 +256,7 @@ def test_level_loss_nodes_equal_the_composition_bit_for_bit(dev):
     per-image arrays, `/ avg_factor` and `* loss_weight` inside the finishing launch, one scaling launch in backward
     (jdet_*_loss_level, jdet_loss_grad_scale) -- against what it replaces: window.reshape(-1) copies + the fused sum +
     two scalar ops (+ three in backward).  Same operations in the same order: loss and gradient EQUAL."""
+    from jdet_amd.models.losses import _level as LV
     from jdet_amd.models.losses import focal_loss as FL
     from jdet_amd.models.losses.smooth_l1_loss import L1Loss, SmoothL1Loss
     rng = np.random.default_rng(11)
@@ -272,7 +273,7 @@ def test_level_loss_nodes_equal_the_composition_bit_for_bit(dev):
         p = torch.from_numpy(rng.standard_normal((M, 5)).astype(np.float32)).to(dev)
         got = {}
         for nodes in (True, False):
-            FL.LEVEL_NODES = nodes
+            LV.LEVEL_NODES = nodes
             try:
                 x1, p1 = x.clone().requires_grad_(True), p.clone().requires_grad_(True)
                 lc = FL.FocalLoss(loss_weight=0.7)(x1, labels[:, s:e], lw[:, s:e], avg_factor=avg)
@@ -281,7 +282,7 @@ def test_level_loss_nodes_equal_the_composition_bit_for_bit(dev):
                 ((lc + lb + l1) * up).backward()
                 got[nodes] = (lc.detach(), lb.detach(), l1.detach(), x1.grad, p1.grad)
             finally:
-                FL.LEVEL_NODES = True
+                LV.LEVEL_NODES = True
         for a, b in zip(got[True], got[False]):
             assert torch.equal(a, b)
     # the node is what ran: no clone of a window, no scalar op (one node per loss)
