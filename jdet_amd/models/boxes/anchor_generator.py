@@ -13,11 +13,8 @@ Lattices are cached per (size, stride, device): tiles of one shape need them onc
 import numpy as np
 import torch
 
+from jdet_amd.utils.general import _pair
 from jdet_amd.utils.registry import BOXES
-
-
-def _pair(x):
-    return tuple(x) if isinstance(x, (tuple, list)) else (x, x)
 
 
 def _octave_scales(octave_base_scale, scales_per_octave):

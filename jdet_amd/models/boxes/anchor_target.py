@@ -33,6 +33,14 @@ def images_to_levels(target, num_level_anchors):
     return level_targets
 
 
+def targets_to_levels(per_image_targets, num_level_anchors, pos_inds_list, neg_inds_list):
+    """the tail of the index-list route of every `anchor_target`: each per-image list of targets split per level, then
+    the numbers of positives and negatives (every image counts at least 1)"""
+    num_total_pos = sum([max(inds.numel(), 1) for inds in pos_inds_list])
+    num_total_neg = sum([max(inds.numel(), 1) for inds in neg_inds_list])
+    return (*[images_to_levels(t, num_level_anchors) for t in per_image_targets], num_total_pos, num_total_neg)
+
+
 def anchor_inside_flags(flat_anchors, valid_flags, img_shape, allowed_border=0):
     img_h, img_w = img_shape[:2]
     if allowed_border >= 0:
@@ -188,10 +196,5 @@ def anchor_target(anchor_list, valid_flag_list, gt_bboxes_list, img_metas, targe
         sampling=sampling, unmap_outputs=unmap_outputs, encode_fn=encode_fn)
     if any([labels is None for labels in all_labels]):
         return None
-    num_total_pos = sum([max(inds.numel(), 1) for inds in pos_inds_list])
-    num_total_neg = sum([max(inds.numel(), 1) for inds in neg_inds_list])
-    labels_list = images_to_levels(all_labels, num_level_anchors)
-    label_weights_list = images_to_levels(all_label_weights, num_level_anchors)
-    bbox_targets_list = images_to_levels(all_bbox_targets, num_level_anchors)
-    bbox_weights_list = images_to_levels(all_bbox_weights, num_level_anchors)
-    return (labels_list, label_weights_list, bbox_targets_list, bbox_weights_list, num_total_pos, num_total_neg)
+    return targets_to_levels((all_labels, all_label_weights, all_bbox_targets, all_bbox_weights), num_level_anchors,
+                             pos_inds_list, neg_inds_list)

@@ -1,13 +1,16 @@
-"""Pieces shared by the rotated single-stage anchor heads (S2ANetHead, RotatedRetinaHead): cached grid
-anchors, valid flags from `pad_shape` (stored (w, h)), the per-level loss, the per-image
-top-k -> decode -> multiclass rotated NMS post-processing and the target-dict parsing.  These are the
-parts that are literally duplicated between s2anet_head.py and rotated_retina_head.py in the reference."""
+"""Pieces shared by the rotated single-stage anchor heads (S2ANetHead, RotatedRetinaHead and its ATSS / KFIoU
+subclasses): cached grid anchors, valid flags from `pad_shape` (stored (w, h)), the loss of one stage
+(targets -> per-level loss; S2ANet runs it twice, FAM and ODM) and the per-image decode in front of the post-processing
+that every single-stage head shares (_dense_head_common.py)."""
 import numpy as np
 import torch
 
-from jdet_amd.models.boxes.box_ops import delta2bbox_rotated, rotated_box_to_poly
-from jdet_amd.ops.nms_rotated import multiclass_nms_rotated
+from jdet_amd.models.boxes.anchor_target import anchor_target, images_to_levels
+from jdet_amd.models.boxes.box_ops import delta2bbox_rotated
+from jdet_amd.utils.general import multi_apply
 from jdet_amd.utils.registry import BOXES, build_from_cfg
+
+from ._dense_head_common import cut_level, merge_levels, nms_polys, parse_targets, per_image
 
 
 class RotatedAnchorHeadMixin:
@@ -48,8 +51,34 @@ class RotatedAnchorHeadMixin:
         anchor_list = [list(multi_level_anchors) for _ in range(len(img_metas))]
         return anchor_list, self._valid_flags(featmap_sizes, img_metas, device)
 
-    def _loss_single(self, loss_cls_fn, loss_bbox_fn, cls_score, bbox_pred, anchors, labels, label_weights,
-                     bbox_targets, bbox_weights, num_total_samples, cfg):
+    anchor_target = staticmethod(anchor_target)     # (RotatedATSSHead: its own, the level sizes go to the assigner)
+
+    def _stage_loss(self, cls_scores, bbox_preds, anchor_list, valid_flag_list, gt_bboxes, gt_labels, img_metas,
+                    gt_bboxes_ignore, cfg, loss_cls_fn, loss_bbox_fn, targets=None, need_anchors=True):
+        """(losses_cls, losses_bbox) per level of one stage, None where the targets are.  targets: what
+        `self.anchor_target` returned for these anchors, else computed here; need_anchors: the per-level anchors, which
+        the loss only reads where it regresses decoded boxes"""
+        num_level_anchors = [anchors.size(0) for anchors in anchor_list[0]]
+        all_anchor_list = [None] * len(num_level_anchors)
+        if need_anchors:
+            concat_anchor_list = [torch.cat(anchor_list[i]) for i in range(len(anchor_list))]
+            all_anchor_list = images_to_levels(concat_anchor_list, num_level_anchors)
+        if targets is None:
+            label_channels = self.cls_out_channels if self.use_sigmoid_cls else 1
+            targets = self.anchor_target(anchor_list, valid_flag_list, gt_bboxes, img_metas, self.target_means,
+                                         self.target_stds, cfg, gt_bboxes_ignore_list=gt_bboxes_ignore,
+                                         gt_labels_list=gt_labels, label_channels=label_channels,
+                                         sampling=self.sampling)
+        if targets is None:
+            return None
+        labels_list, label_weights_list, bbox_targets_list, bbox_weights_list, num_total_pos, num_total_neg = targets
+        num_total_samples = num_total_pos + num_total_neg if self.sampling else num_total_pos
+        return multi_apply(self._loss_single, cls_scores, bbox_preds, all_anchor_list, labels_list, label_weights_list,
+                           bbox_targets_list, bbox_weights_list, loss_cls_fn=loss_cls_fn, loss_bbox_fn=loss_bbox_fn,
+                           num_total_samples=num_total_samples, cfg=cfg)
+
+    def _loss_single(self, cls_score, bbox_pred, anchors, labels, label_weights, bbox_targets, bbox_weights,
+                     loss_cls_fn, loss_bbox_fn, num_total_samples, cfg):
         # The level's targets are column windows [:, s:e] of the per-image arrays.  FocalLoss / SmoothL1Loss / L1Loss read
         # such windows in place (one node per level and loss, models/losses/focal_loss.py: _FocalLevel); flattening them
         # here -- what the reference does, s2anet_head.py:L441-450 -- costs a copy per window (40 per S2ANet step).
@@ -74,11 +103,7 @@ class RotatedAnchorHeadMixin:
             bbox_weights = bbox_weights.reshape(-1, 5)
         bbox_pred = bbox_pred.permute(0, 2, 3, 1).reshape(-1, 5)
         if cfg.get("reg_decoded_bbox", False):
-            bbox_coder_cfg = cfg.get("bbox_coder", "")
-            if bbox_coder_cfg == "":
-                bbox_coder_cfg = dict(type="DeltaXYWHBBoxCoder")
-            bbox_coder = build_from_cfg(bbox_coder_cfg, BOXES)
-            bbox_pred = bbox_coder.decode(anchors.reshape(-1, 5), bbox_pred)
+            bbox_pred = self._bbox_coder(cfg).decode(anchors.reshape(-1, 5), bbox_pred)
         loss_bbox = loss_bbox_fn(bbox_pred, bbox_targets, bbox_weights, avg_factor=num_total_samples)
         return loss_cls, loss_bbox
 
@@ -88,45 +113,36 @@ class RotatedAnchorHeadMixin:
             bbox_coder_cfg = dict(type="DeltaXYWHBBoxCoder")
         return build_from_cfg(bbox_coder_cfg, BOXES)
 
+    def _level_scores(self, cls_score):
+        """a level's (A * C, H, W) map -> (scores (n, C), rank); rank() is the score the `nms_pre` cut ranks the rows
+        by, the best foreground class"""
+        cls_score = cls_score.permute(1, 2, 0).reshape(-1, self.cls_out_channels)
+        if self.use_sigmoid_cls:
+            scores = cls_score.sigmoid()
+            return scores, lambda: scores.max(dim=1).values
+        scores = cls_score.softmax(-1)
+        return scores, lambda: scores[:, 1:].max(dim=1).values
+
     def get_bboxes_single(self, cls_score_list, bbox_pred_list, mlvl_anchors, img_shape, scale_factor, cfg,
                           rescale=False):
         assert len(cls_score_list) == len(bbox_pred_list) == len(mlvl_anchors)
         mlvl_bboxes, mlvl_scores = [], []
         for cls_score, bbox_pred, anchors in zip(cls_score_list, bbox_pred_list, mlvl_anchors):
             assert cls_score.shape[-2:] == bbox_pred.shape[-2:]
-            cls_score = cls_score.permute(1, 2, 0).reshape(-1, self.cls_out_channels)
-            scores = cls_score.sigmoid() if self.use_sigmoid_cls else cls_score.softmax(-1)
+            scores, rank = self._level_scores(cls_score)
             bbox_pred = bbox_pred.permute(1, 2, 0).reshape(-1, 5)
-            nms_pre = cfg.get("nms_pre", -1)
-            if nms_pre > 0 and scores.shape[0] > nms_pre:
-                max_scores = scores.max(dim=1).values if self.use_sigmoid_cls else scores[:, 1:].max(dim=1).values
-                _, topk_inds = max_scores.topk(nms_pre)
-                anchors = anchors[topk_inds, :]
-                bbox_pred = bbox_pred[topk_inds, :]
-                scores = scores[topk_inds, :]
+            anchors, bbox_pred, scores = cut_level(cfg.get("nms_pre", -1), rank, anchors, bbox_pred, scores)
             mlvl_bboxes.append(delta2bbox_rotated(anchors, bbox_pred, self.target_means, self.target_stds, img_shape))
             mlvl_scores.append(scores)
-        mlvl_bboxes = torch.cat(mlvl_bboxes)
-        if rescale:
-            mlvl_bboxes[..., :4] /= scale_factor
-        mlvl_scores = torch.cat(mlvl_scores)
-        if self.use_sigmoid_cls:
-            padding = mlvl_scores.new_zeros((mlvl_scores.shape[0], 1))
-            mlvl_scores = torch.cat([padding, mlvl_scores], dim=1)
-        det_bboxes, det_labels = multiclass_nms_rotated(mlvl_bboxes, mlvl_scores, cfg.score_thr, cfg.nms,
-                                                        cfg.max_per_img)
-        boxes, scores = det_bboxes[:, :5], det_bboxes[:, 5]
-        return rotated_box_to_poly(boxes), scores, det_labels
+        return nms_polys(*merge_levels(mlvl_bboxes, mlvl_scores, scale_factor, rescale, self.use_sigmoid_cls), cfg)
+
+    def _get_bboxes(self, cls_scores, bbox_preds, anchor_list, img_metas, rescale):
+        """`get_bboxes_single` of every image on its own anchors (per level) with the test cfg"""
+        cfg = self.test_cfg.copy()
+        return per_image(lambda b, cls_score_list, bbox_pred_list: self.get_bboxes_single(
+            cls_score_list, bbox_pred_list, anchor_list[b], img_metas[b]["img_shape"], img_metas[b]["scale_factor"],
+            cfg, rescale), len(img_metas), cls_scores, bbox_preds)
 
     def parse_targets(self, targets, is_train=True):
-        img_metas, gt_bboxes, gt_bboxes_ignore, gt_labels = [], [], [], []
-        for target in targets:
-            if is_train:
-                gt_bboxes.append(target["rboxes"])
-                gt_labels.append(target["labels"])
-                gt_bboxes_ignore.append(target["rboxes_ignore"])
-            img_metas.append(dict(img_shape=target["img_size"][::-1], scale_factor=target["scale_factor"],
-                                  pad_shape=target["pad_shape"]))
-        if not is_train:
-            return img_metas
-        return gt_bboxes, gt_labels, img_metas, gt_bboxes_ignore
+        parsed = parse_targets(targets, is_train)
+        return parsed if is_train else parsed[2]

@@ -8,28 +8,33 @@ Two routes for targets and loss, same values:
            the geometry in csrc/poly_iou_loss.hip), the counts stay on the device: no nonzero(), no host sync.
   general  the reference's tensor program per image ((points x gts) tensors, argmin, gathers) and its gather of the
            positives through nonzero().
+Both routes return their losses together with the intermediates behind them (`_DenseLoss`, `_GeneralLoss`): H2RBoxHead
+adds its consistency term to them and overrides only the box-loss hooks.  Padded gts and post-processing are the ones
+every single-stage head shares (_dense_head_common.py).
 Where the reference leaves a rule open or gets it wrong (ties, background targets, images without gts) both routes
 follow include/jdet_hip_fcos.h."""
 import ctypes
+from collections import namedtuple
 
 import torch
 from torch import nn
 
 from jdet_amd import _lib as L
-from jdet_amd.models.boxes.box_ops import distance2obb, mintheta_obb, rotated_box_to_poly
+from jdet_amd.models.boxes.box_ops import distance2obb, mintheta_obb
 from jdet_amd.models.utils.modules import ConvModule
 from jdet_amd.models.utils.weight_init import bias_init_with_prob, normal_init
-from jdet_amd.ops.nms_rotated import multiclass_nms_rotated
 from jdet_amd.utils.general import multi_apply
 from jdet_amd.utils.registry import HEADS, LOSSES, build_from_cfg
 
-from .s2anet_head import _cfg
+from ._dense_head_common import _cfg, cut_level, device_counts, merge_levels, nms_polys, pad_gts, per_image
 
 INF = 1e8
 
-def _device_counts(counts, device):
-    """(B,) int32 device tensor of the images' gt counts: a pinned host tensor copied asynchronously (no host sync)"""
-    return torch.tensor(counts, dtype=torch.int32).pin_memory().to(device, non_blocking=True)
+# what the shared part of a route hands to a subclass that adds a term (H2RBoxHead): the three losses and the
+# intermediates they were computed from
+_DenseLoss = namedtuple("_DenseLoss", "losses preds preds_aug labels2d centerness2d")
+_GeneralLoss = namedtuple("_GeneralLoss", "losses pos_inds pos_bbox_preds pos_decoded_bbox_preds "
+                                          "pos_centerness_targets focal_labels flatten_points")
 
 
 def fcos_targets_device(featmap_sizes, strides, regress_ranges, gt, gt_labels, gt_count, num_classes, norm_on_bbox=False,
@@ -197,22 +202,10 @@ class FCOSHead(nn.Module):
 
     def _dense_targets(self, featmap_sizes, gt_bboxes_list, gt_labels_list):
         """labels (B, N) int32, bbox_targets (B, N, 5), centerness (B, N): one launch, image-major"""
-        B = len(gt_bboxes_list)
-        counts = [int(g.shape[0]) for g in gt_bboxes_list]
-        Kmax = max(max(counts), 1)
-        dev = gt_bboxes_list[0].device
-        if all(c == Kmax for c in counts):
-            gt = torch.stack(gt_bboxes_list)
-            gl = torch.stack([t.to(torch.int32) for t in gt_labels_list])
-        else:
-            gt = torch.zeros((B, Kmax, 5), dtype=torch.float32, device=dev)
-            gl = torch.zeros((B, Kmax), dtype=torch.int32, device=dev)
-            for b, (g, t) in enumerate(zip(gt_bboxes_list, gt_labels_list)):
-                if counts[b]:
-                    gt[b, :counts[b]] = g
-                    gl[b, :counts[b]] = t.to(torch.int32)
-        return fcos_targets_device(featmap_sizes, self.strides, self.regress_ranges, gt, gl, _device_counts(counts, dev),
-                                   self.num_classes, self.norm_on_bbox, self.center_sampling, self.center_sample_radius)
+        gt, gl, counts = pad_gts(gt_bboxes_list, gt_labels_list, 5)
+        return fcos_targets_device(featmap_sizes, self.strides, self.regress_ranges, gt, gl,
+                                   device_counts(counts, gt.device), self.num_classes, self.norm_on_bbox,
+                                   self.center_sampling, self.center_sample_radius)
 
     def get_targets(self, points, targets, dense=True, featmap_sizes=None):
         """labels and [l, t, r, b, theta] targets of every level, the images concatenated inside a level"""
@@ -323,16 +316,30 @@ class FCOSHead(nn.Module):
     # ------------------------------------------------------------------------------------------------------------ loss
     def loss(self, cls_scores, bbox_preds, theta_preds, centernesses, targets):
         assert len(cls_scores) == len(bbox_preds) == len(centernesses)
+        outs = (cls_scores, bbox_preds, theta_preds, centernesses)
         featmap_sizes = [tuple(featmap.shape[-2:]) for featmap in cls_scores]
-        dev = cls_scores[0].device
-        all_level_points = self.get_points(featmap_sizes, bbox_preds[0].dtype, dev)
-        num_imgs = cls_scores[0].size(0)
+        all_level_points = self.get_points(featmap_sizes, bbox_preds[0].dtype, cls_scores[0].device)
         gt_bboxes_list = [t["rboxes"] for t in targets]
         gt_labels_list = [t["labels"] for t in targets]
         if cls_scores[0].is_cuda and bbox_preds[0].dtype == torch.float32 and \
                 self._dense_ok(gt_bboxes_list, gt_labels_list):
-            return self._loss_dense(cls_scores, bbox_preds, theta_preds, centernesses, featmap_sizes, all_level_points,
-                                    gt_bboxes_list, gt_labels_list)
+            return self._dense_parts(outs, None, featmap_sizes, all_level_points, gt_bboxes_list, gt_labels_list).losses
+        return self._general_parts(outs, all_level_points, targets).losses
+
+    # the two points where a subclass's box loss differs (H2RBoxHead: horizontal boxes, its own normaliser)
+    def _loss_bbox_dense(self, decoded_preds, decoded_targets, weight):
+        weight_sum = weight.sum()
+        return self.loss_bbox(decoded_preds, decoded_targets, weight=weight,
+                              avg_factor=torch.where(weight_sum > 0, weight_sum, torch.ones_like(weight_sum)))
+
+    def _loss_bbox_general(self, decoded_preds, decoded_targets, weight):
+        return self.loss_bbox(decoded_preds, decoded_targets, weight=weight, avg_factor=weight.sum(), fused=False)
+
+    def _general_parts(self, outs, all_level_points, targets):
+        """the reference's route: level-major rows, the positives gathered through nonzero().  Without positives the
+        box and centerness losses are empty sums and the intermediates of the positives None."""
+        cls_scores, bbox_preds, theta_preds, centernesses = outs
+        num_imgs = cls_scores[0].size(0)
         labels, bbox_targets = self.get_targets(all_level_points, targets, dense=False)
         flatten_cls_scores = torch.cat([c.permute(0, 2, 3, 1).reshape(-1, self.num_classes) for c in cls_scores])
         flatten_bbox_preds = torch.cat([b.permute(0, 2, 3, 1).reshape(-1, 4) for b in bbox_preds])
@@ -350,32 +357,34 @@ class FCOSHead(nn.Module):
         loss_cls = self.loss_cls(flatten_cls_scores, focal_labels, avg_factor=num_pos + num_imgs)
         pos_bbox_preds = flatten_bbox_preds[pos_inds]
         pos_centerness = flatten_centerness[pos_inds]
-        if num_pos > 0:
-            pos_bbox_targets = flatten_bbox_targets[pos_inds]
-            pos_centerness_targets = self.centerness_target(pos_bbox_targets)
-            pos_points = flatten_points[pos_inds]
-            pos_decoded_bbox_preds = distance2obb(pos_points, pos_bbox_preds)
-            pos_decoded_target_preds = distance2obb(pos_points, pos_bbox_targets)
-            loss_bbox = self.loss_bbox(pos_decoded_bbox_preds, pos_decoded_target_preds, weight=pos_centerness_targets,
-                                       avg_factor=pos_centerness_targets.sum(), fused=False)
-            loss_centerness = self.loss_centerness(pos_centerness, pos_centerness_targets)
-        else:
-            loss_bbox = pos_bbox_preds.sum()
-            loss_centerness = pos_centerness.sum()
-        return dict(loss_cls=loss_cls, loss_bbox=loss_bbox, loss_centerness=loss_centerness)
+        if num_pos == 0:
+            losses = dict(loss_cls=loss_cls, loss_bbox=pos_bbox_preds.sum(), loss_centerness=pos_centerness.sum())
+            return _GeneralLoss(losses, pos_inds, pos_bbox_preds, None, None, focal_labels, flatten_points)
+        pos_bbox_targets = flatten_bbox_targets[pos_inds]
+        pos_centerness_targets = self.centerness_target(pos_bbox_targets)
+        pos_points = flatten_points[pos_inds]
+        pos_decoded_bbox_preds = distance2obb(pos_points, pos_bbox_preds)
+        pos_decoded_target_preds = distance2obb(pos_points, pos_bbox_targets)
+        loss_bbox = self._loss_bbox_general(pos_decoded_bbox_preds, pos_decoded_target_preds, pos_centerness_targets)
+        loss_centerness = self.loss_centerness(pos_centerness, pos_centerness_targets)
+        losses = dict(loss_cls=loss_cls, loss_bbox=loss_bbox, loss_centerness=loss_centerness)
+        return _GeneralLoss(losses, pos_inds, pos_bbox_preds, pos_decoded_bbox_preds, pos_centerness_targets,
+                            focal_labels, flatten_points)
 
-    def _loss_dense(self, cls_scores, bbox_preds, theta_preds, centernesses, featmap_sizes, all_level_points,
-                    gt_bboxes_list, gt_labels_list):
+    def _dense_parts(self, outs, outs_aug, featmap_sizes, all_level_points, gt_bboxes_list, gt_labels_list):
         """every loss over all points in image-major order (the order jdet_fcos_targets writes); nothing leaves the
-        device"""
+        device.  outs_aug: (bbox_preds, theta_preds) of a second view (H2RBoxHead) or None: flattened alike."""
+        cls_scores, bbox_preds, theta_preds, centernesses = outs
         B = cls_scores[0].size(0)
         rows = lambda ts, c: torch.cat([t.permute(0, 2, 3, 1).reshape(B, -1, c) for t in ts], dim=1)  # noqa: E731
         flatten_cls_scores = rows(cls_scores, self.num_classes).reshape(-1, self.num_classes)
-        flatten_bbox_preds = torch.cat([rows(bbox_preds, 4), rows(theta_preds, 1)], dim=2).reshape(-1, 5)
+        preds = torch.cat([rows(bbox_preds, 4), rows(theta_preds, 1)], dim=2)                 # (B, N, 5)
+        preds_aug = None if outs_aug is None else torch.cat([rows(outs_aug[0], 4), rows(outs_aug[1], 1)], dim=2)
+        flatten_bbox_preds = preds.reshape(-1, 5)
         flatten_centerness = rows(centernesses, 1).reshape(-1)
-        labels, bbox_targets, centerness_targets = self._dense_targets(featmap_sizes, gt_bboxes_list, gt_labels_list)
-        labels, bbox_targets, centerness_targets = labels.reshape(-1), bbox_targets.reshape(-1, 5), \
-            centerness_targets.reshape(-1)
+        labels2d, bbox_targets, centerness2d = self._dense_targets(featmap_sizes, gt_bboxes_list, gt_labels_list)
+        labels, bbox_targets, centerness_targets = labels2d.reshape(-1), bbox_targets.reshape(-1, 5), \
+            centerness2d.reshape(-1)
         flatten_points = torch.cat(all_level_points).repeat(B, 1)
         pos = (labels >= 0) & (labels < self.num_classes)      # the general route's predicate
         num_pos = pos.sum().to(torch.float32)
@@ -383,69 +392,45 @@ class FCOSHead(nn.Module):
         loss_cls = self.loss_cls(flatten_cls_scores, focal_labels, avg_factor=(num_pos + B).reshape(1))
         decoded_preds = distance2obb(flatten_points, flatten_bbox_preds)
         decoded_targets = distance2obb(flatten_points, bbox_targets)
-        weight_sum = centerness_targets.sum()
-        loss_bbox = self.loss_bbox(decoded_preds, decoded_targets, weight=centerness_targets,
-                                   avg_factor=torch.where(weight_sum > 0, weight_sum, torch.ones_like(weight_sum)))
+        loss_bbox = self._loss_bbox_dense(decoded_preds, decoded_targets, centerness_targets)
         loss_centerness = self.loss_centerness(flatten_centerness, centerness_targets, weight=pos.to(torch.float32),
                                                avg_factor=num_pos.clamp(min=1.0))
-        return dict(loss_cls=loss_cls, loss_bbox=loss_bbox, loss_centerness=loss_centerness)
+        losses = dict(loss_cls=loss_cls, loss_bbox=loss_bbox, loss_centerness=loss_centerness)
+        return _DenseLoss(losses, preds, preds_aug, labels2d, centerness2d)
 
     # ------------------------------------------------------------------------------------------------------- inference
     def get_bboxes(self, cls_scores, bbox_preds, theta_preds, centernesses, targets, rescale=True):
         assert len(cls_scores) == len(bbox_preds)
-        num_levels = len(cls_scores)
         featmap_sizes = [tuple(featmap.shape[-2:]) for featmap in cls_scores]
         mlvl_points = self.get_points(featmap_sizes, bbox_preds[0].dtype, cls_scores[0].device)
-        result_list = []
-        for img_id in range(len(targets)):
-            cls_score_list = [cls_scores[i][img_id].detach() for i in range(num_levels)]
-            bbox_pred_list = [bbox_preds[i][img_id].detach() for i in range(num_levels)]
-            theta_pred_list = [theta_preds[i][img_id].detach() for i in range(num_levels)]
-            centerness_pred_list = [centernesses[i][img_id].detach() for i in range(num_levels)]
-            img_shape = targets[img_id]["img_size"]
-            scale_factor = targets[img_id]["scale_factor"]
-            result_list.append(self._get_bboxes_single(cls_score_list, bbox_pred_list, theta_pred_list,
-                                                       centerness_pred_list, mlvl_points, img_shape, scale_factor,
-                                                       rescale))
-        return result_list
+        return per_image(lambda b, *levels: self._get_bboxes_single(
+            *levels, mlvl_points, targets[b]["img_size"], targets[b]["scale_factor"], rescale), len(targets),
+            cls_scores, bbox_preds, theta_preds, centernesses)
+
+    def _level_scores(self, cls_score, centerness):
+        """a level's (C, H, W) and (1, H, W) maps -> (scores (n, C), centerness (n,) with the cfg's `centerness_factor`
+        added, rank); rank() is the score the `nms_pre` cut ranks the rows by: the best class score times the
+        centerness"""
+        scores = cls_score.permute(1, 2, 0).reshape(-1, self.num_classes).sigmoid()
+        centerness = centerness.permute(1, 2, 0).reshape(-1).sigmoid()
+        centerness = centerness + self.test_cfg.get("centerness_factor", 0.)
+        return scores, centerness, lambda: (scores * centerness[:, None]).max(dim=1).values
 
     def _get_bboxes_single(self, cls_scores, bbox_preds, theta_preds, centernesses, mlvl_points, img_shape, scale_factor,
                            rescale=False):
         cfg = self.test_cfg
         assert len(cls_scores) == len(bbox_preds) == len(mlvl_points)
-        mlvl_bboxes = []
-        mlvl_scores = []
-        mlvl_centerness = []
+        mlvl_bboxes, mlvl_scores, mlvl_centerness = [], [], []
         for cls_score, bbox_pred, theta_pred, centerness, points in zip(cls_scores, bbox_preds, theta_preds,
                                                                         centernesses, mlvl_points):
             assert cls_score.shape[-2:] == bbox_pred.shape[-2:]
-            scores = cls_score.permute(1, 2, 0).reshape(-1, self.num_classes).sigmoid()
-            centerness = centerness.permute(1, 2, 0).reshape(-1).sigmoid()
+            scores, centerness, rank = self._level_scores(cls_score, centerness)
             theta_pred = theta_pred.permute(1, 2, 0).reshape(-1, 1)
             bbox_pred = bbox_pred.permute(1, 2, 0).reshape(-1, 4)
             bbox_pred = torch.cat([bbox_pred, theta_pred], dim=1)
-            nms_pre = cfg.get("nms_pre", -1)
-            centerness = centerness + cfg.get("centerness_factor", 0.)
-            if nms_pre > 0 and scores.shape[0] > nms_pre:
-                max_scores = (scores * centerness[:, None]).max(dim=1).values
-                _, topk_inds = max_scores.topk(nms_pre)
-                bbox_pred = bbox_pred[topk_inds, :]
-                scores = scores[topk_inds, :]
-                points = points[topk_inds, :]
-                centerness = centerness[topk_inds]
+            bbox_pred, scores, points, centerness = cut_level(cfg.get("nms_pre", -1), rank, bbox_pred, scores, points,
+                                                              centerness)
             mlvl_bboxes.append(distance2obb(points, bbox_pred, max_shape=img_shape))
             mlvl_scores.append(scores)
             mlvl_centerness.append(centerness)
-        mlvl_bboxes = torch.cat(mlvl_bboxes)
-        if rescale:
-            mlvl_bboxes = torch.cat([mlvl_bboxes[..., :4] / scale_factor, mlvl_bboxes[..., 4:]], dim=-1)
-        mlvl_scores = torch.cat(mlvl_scores)
-        padding = mlvl_scores.new_zeros((mlvl_scores.shape[0], 1))
-        mlvl_centerness = torch.cat(mlvl_centerness)
-        mlvl_scores = torch.cat([padding, mlvl_scores], dim=1)
-        det_bboxes, det_labels = multiclass_nms_rotated(mlvl_bboxes, mlvl_scores, cfg.score_thr, cfg.nms,
-                                                        cfg.max_per_img, score_factors=mlvl_centerness)
-        boxes = det_bboxes[:, :5]
-        scores = det_bboxes[:, 5]
-        polys = rotated_box_to_poly(boxes)
-        return polys, scores, det_labels
+        return nms_polys(*merge_levels(mlvl_bboxes, mlvl_scores, scale_factor, rescale, True, mlvl_centerness), cfg)

@@ -1,11 +1,14 @@
 """H2RBox head: FCOSHead plus a second, rotated view of the same batch and a consistency loss between the two views.
 Mirrors python/jdet/models/roi_heads/h2rbox_head.py: H2RBoxHead L30-860 (obb2xyxy L198-214, forward_aug L216-235,
 execute_train L237-244, _process_rotation_agnostic L312-319, loss L321-519, the rect_classes rewrite L667-674).
-Everything else -- towers, Scale, points, targets, inference -- is FCOSHead's.
+Everything else -- towers, Scale, points, targets, inference -- is FCOSHead's, and so are the three losses both heads
+have: FCOSHead._dense_parts / _general_parts compute them through the `_loss_bbox_dense` / `_loss_bbox_general` hooks
+overridden here (horizontal boxes, the reference's normalisers) and hand back the intermediates the consistency term
+is computed from.
 
 Two routes for the loss, same values, behind FCOSHead's `dense` switch:
   dense    device fp32 tensors -- what the config hits.  Targets by jdet_fcos_targets; focal loss, the horizontal IoU
-           loss and the centerness BCE over ALL points as in FCOSHead._loss_dense; the consistency branch in one launch
+           loss and the centerness BCE over ALL points as in FCOSHead._dense_parts; the consistency branch in one launch
            over all points (csrc/h2rbox_aug_loss.hip through H2RBoxLoss.dense): cell map, gather of view 2, decoded
            boxes, rotated targets, the three terms; the sums, the scalar minimum and every count stay on the device --
            no nonzero(), no .any(), no host sync.
@@ -110,12 +113,10 @@ class H2RBoxHead(FCOSHead):
 
     def loss(self, outs, outs_aug, rot, targets):
         cls_scores, bbox_preds, theta_preds, centernesses = outs
-        bbox_preds_aug, theta_preds_aug = outs_aug
         assert len(cls_scores) == len(bbox_preds) == len(centernesses)
         rot = float(torch.tensor(float(rot), dtype=torch.float32))    # rounded to float once: what the kernel receives
         featmap_sizes = [tuple(featmap.shape[-2:]) for featmap in cls_scores]
-        dev = cls_scores[0].device
-        all_level_points = self.get_points(featmap_sizes, bbox_preds[0].dtype, dev)
+        all_level_points = self.get_points(featmap_sizes, bbox_preds[0].dtype, cls_scores[0].device)
         gt_bboxes_list = [t["rboxes"] for t in targets]
         gt_labels_list = [t["labels"] for t in targets]
         if cls_scores[0].is_cuda and bbox_preds[0].dtype == torch.float32 and self._aug_dense_ok() and \
@@ -124,63 +125,31 @@ class H2RBoxHead(FCOSHead):
                                         gt_labels_list)
         return self._loss_general(outs, outs_aug, rot, featmap_sizes, all_level_points, targets)
 
+    # FCOSHead's box loss on the circumscribed horizontal boxes, with the reference's normalisers
+    def _loss_bbox_dense(self, decoded_preds, decoded_targets, weight):
+        return self.loss_bbox(self.obb2xyxy(decoded_preds), self.obb2xyxy(decoded_targets), weight=weight,
+                              avg_factor=weight.sum().clamp(min=1e-6))
+
+    def _loss_bbox_general(self, decoded_preds, decoded_targets, weight):
+        return self.loss_bbox(self.obb2xyxy(decoded_preds), self.obb2xyxy(decoded_targets), weight=weight,
+                              avg_factor=weight.sum().detach().clamp(min=1e-6))
+
     def _loss_dense_aug(self, outs, outs_aug, rot, featmap_sizes, all_level_points, gt_bboxes_list, gt_labels_list):
-        """every loss over all points in image-major order (the order jdet_fcos_targets writes); nothing leaves the
-        device"""
-        cls_scores, bbox_preds, theta_preds, centernesses = outs
-        bbox_preds_aug, theta_preds_aug = outs_aug
-        B = cls_scores[0].size(0)
-        rows = lambda ts, c: torch.cat([t.permute(0, 2, 3, 1).reshape(B, -1, c) for t in ts], dim=1)  # noqa: E731
-        flatten_cls_scores = rows(cls_scores, self.num_classes).reshape(-1, self.num_classes)
-        preds = torch.cat([rows(bbox_preds, 4), rows(theta_preds, 1)], dim=2)                 # (B, N, 5)
-        preds_aug = torch.cat([rows(bbox_preds_aug, 4), rows(theta_preds_aug, 1)], dim=2)
-        flatten_bbox_preds = preds.reshape(-1, 5)
-        flatten_centerness = rows(centernesses, 1).reshape(-1)
-        labels2d, bbox_targets, centerness2d = self._dense_targets(featmap_sizes, gt_bboxes_list, gt_labels_list)
-        labels, bbox_targets, centerness_targets = labels2d.reshape(-1), bbox_targets.reshape(-1, 5), \
-            centerness2d.reshape(-1)
-        flatten_points = torch.cat(all_level_points).repeat(B, 1)
-        pos = (labels >= 0) & (labels < self.num_classes)
-        num_pos = pos.sum().to(torch.float32)
-        focal_labels = torch.where(pos, labels + 1, torch.zeros_like(labels))
-        loss_cls = self.loss_cls(flatten_cls_scores, focal_labels, avg_factor=(num_pos + B).reshape(1))
-        decoded_preds = distance2obb(flatten_points, flatten_bbox_preds)
-        decoded_targets = distance2obb(flatten_points, bbox_targets)
-        loss_bbox = self.loss_bbox(self.obb2xyxy(decoded_preds), self.obb2xyxy(decoded_targets),
-                                   weight=centerness_targets, avg_factor=centerness_targets.sum().clamp(min=1e-6))
-        loss_centerness = self.loss_centerness(flatten_centerness, centerness_targets, weight=pos.to(torch.float32),
-                                               avg_factor=num_pos.clamp(min=1.0))
-        loss_bbox_aug, _ = self.loss_bbox_aug.dense(featmap_sizes, self.strides, preds, preds_aug, centerness2d, labels2d,
-                                                    self.rotation_agnostic_classes, rot, self.crop_size)
-        return dict(loss_cls=loss_cls, loss_bbox=loss_bbox, loss_centerness=loss_centerness,
-                    loss_bbox_aug=loss_bbox_aug)
+        """FCOSHead's dense losses + the consistency term in one launch over all points"""
+        d = self._dense_parts(outs, outs_aug, featmap_sizes, all_level_points, gt_bboxes_list, gt_labels_list)
+        loss_bbox_aug, _ = self.loss_bbox_aug.dense(featmap_sizes, self.strides, d.preds, d.preds_aug, d.centerness2d,
+                                                    d.labels2d, self.rotation_agnostic_classes, rot, self.crop_size)
+        return dict(d.losses, loss_bbox_aug=loss_bbox_aug)
 
     def _loss_general(self, outs, outs_aug, rot, featmap_sizes, all_level_points, targets):
-        cls_scores, bbox_preds, theta_preds, centernesses = outs
+        """FCOSHead's general losses + the consistency term on the positives whose cell lies inside view two"""
         bbox_preds_aug, theta_preds_aug = outs_aug
-        labels, bbox_targets = self.get_targets(all_level_points, targets, dense=False)
-        num_imgs = cls_scores[0].size(0)
-        flatten_cls_scores = torch.cat([c.permute(0, 2, 3, 1).reshape(-1, self.num_classes) for c in cls_scores])
-        flatten_bbox_preds = torch.cat([b.permute(0, 2, 3, 1).reshape(-1, 4) for b in bbox_preds])
-        flatten_theta_preds = torch.cat([t.permute(0, 2, 3, 1).reshape(-1, 1) for t in theta_preds])
-        flatten_centerness = torch.cat([c.permute(0, 2, 3, 1).reshape(-1) for c in centernesses])
-        flatten_labels = torch.cat(labels)
-        flatten_bbox_targets = torch.cat(bbox_targets)
-        flatten_points = torch.cat([points.repeat(num_imgs, 1) for points in all_level_points])
-        flatten_bbox_preds = torch.cat([flatten_bbox_preds, flatten_theta_preds], dim=1)
-        bg_class_ind = self.num_classes
-        pos_inds = ((flatten_labels >= 0) & (flatten_labels < bg_class_ind)).nonzero().reshape(-1)
-        num_pos = len(pos_inds)
-        # FocalLoss: 1-based classes, 0 = background
-        flatten_labels = torch.where(flatten_labels == bg_class_ind, torch.zeros_like(flatten_labels), flatten_labels + 1)
-        loss_cls = self.loss_cls(flatten_cls_scores, flatten_labels, avg_factor=num_pos + num_imgs)
-        pos_bbox_preds = flatten_bbox_preds[pos_inds]
-        pos_centerness = flatten_centerness[pos_inds]
-        if num_pos == 0:
-            zero = pos_bbox_preds.sum()
-            return dict(loss_cls=loss_cls, loss_bbox=zero, loss_centerness=pos_centerness.sum(), loss_bbox_aug=zero)
-        pos_bbox_targets = flatten_bbox_targets[pos_inds]
-        pos_centerness_targets = self.centerness_target(pos_bbox_targets)
+        num_imgs = outs[0][0].size(0)
+        g = self._general_parts(outs, all_level_points, targets)
+        losses, pos_inds, pos_bbox_preds, flatten_points = g.losses, g.pos_inds, g.pos_bbox_preds, g.flatten_points
+        pos_decoded_bbox_preds, pos_centerness_targets = g.pos_decoded_bbox_preds, g.pos_centerness_targets
+        if len(pos_inds) == 0:
+            return dict(losses, loss_bbox_aug=losses["loss_bbox"])
         cosa, sina = math.cos(rot), math.sin(rot)
         tf_T = torch.tensor([[cosa, sina], [-sina, cosa]], dtype=torch.float32, device=pos_inds.device)
         tf_T = tf_T.to(pos_bbox_preds.dtype)
@@ -204,18 +173,9 @@ class H2RBoxHead(FCOSHead):
             pos_inds_aug_v[level_mask] = xy_valid_aug
             pos_inds_aug.append(pos_ind_aug[xy_valid_aug] + offset)
             offset += num_imgs * h * w
-        has_valid_aug = bool(pos_inds_aug_v.any())
-        pos_points = flatten_points[pos_inds]
-        pos_labels = flatten_labels[pos_inds]
-        pos_decoded_bbox_preds = distance2obb(pos_points, pos_bbox_preds)
-        pos_decoded_target_preds = distance2obb(pos_points, pos_bbox_targets)
-        loss_bbox = self.loss_bbox(self.obb2xyxy(pos_decoded_bbox_preds), self.obb2xyxy(pos_decoded_target_preds),
-                                   weight=pos_centerness_targets,
-                                   avg_factor=pos_centerness_targets.sum().detach().clamp(min=1e-6))
-        loss_centerness = self.loss_centerness(pos_centerness, pos_centerness_targets)
-        if not has_valid_aug:
-            return dict(loss_cls=loss_cls, loss_bbox=loss_bbox, loss_centerness=loss_centerness,
-                        loss_bbox_aug=pos_bbox_preds[:0].sum())
+        if not bool(pos_inds_aug_v.any()):
+            return dict(losses, loss_bbox_aug=pos_bbox_preds[:0].sum())
+        pos_labels = g.focal_labels[pos_inds]
         pos_inds_aug = torch.cat(pos_inds_aug)
         flatten_bbox_preds_aug = torch.cat([b.permute(0, 2, 3, 1).reshape(-1, 4) for b in bbox_preds_aug])
         flatten_theta_preds_aug = torch.cat([t.permute(0, 2, 3, 1).reshape(-1, 1) for t in theta_preds_aug])
@@ -224,7 +184,7 @@ class H2RBoxHead(FCOSHead):
         pos_points_aug = flatten_points[pos_inds_aug]
         pos_decoded_bbox_preds_aug = distance2obb(pos_points_aug, pos_bbox_preds_aug)
         _h, _w = self.crop_size
-        _ctr = pos_points.new_tensor([[(_w - 1) / 2, (_h - 1) / 2]])
+        _ctr = flatten_points.new_tensor([[(_w - 1) / 2, (_h - 1) / 2]])
         _xy = pos_decoded_bbox_preds[pos_inds_aug_v, :2]
         _wh = pos_decoded_bbox_preds[pos_inds_aug_v, 2:4]
         pos_angle_targets_aug = pos_decoded_bbox_preds[pos_inds_aug_v, 4:] + rot
@@ -239,8 +199,7 @@ class H2RBoxHead(FCOSHead):
         centerness_denorm_aug = pos_centerness_targets_aug.sum().detach().clamp(min=1.0)
         loss_bbox_aug = self.loss_bbox_aug(pos_decoded_bbox_preds_aug, pos_decoded_target_preds_aug,
                                            weight=pos_centerness_targets_aug, avg_factor=centerness_denorm_aug)
-        return dict(loss_cls=loss_cls, loss_bbox=loss_bbox, loss_centerness=loss_centerness,
-                    loss_bbox_aug=loss_bbox_aug)
+        return dict(losses, loss_bbox_aug=loss_bbox_aug)
 
     # -------------------------------------------------------------------------------------------------------- inference
     def _get_bboxes_single(self, *args, **kwargs):

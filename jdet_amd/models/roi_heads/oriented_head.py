@@ -25,16 +25,12 @@ from jdet_amd.models.boxes.fixed_shape import (DUMMY_OBB, class_rows, label_weig
                                                with_image_index)
 from jdet_amd.models.utils.modules import ConvModule
 from jdet_amd.ops.bbox_transforms import get_bbox_dim, obb2poly
-from jdet_amd.utils.general import const_like
+from jdet_amd.utils.general import _pair, const_like
 from jdet_amd.utils.registry import BOXES, HEADS, LOSSES, ROI_EXTRACTORS, build_from_cfg
 
 from jdet_amd.ops.linear import Linear
 
 from .roi_feature_linear import RoIFeatureLinear
-
-
-def _pair(x):
-    return tuple(x) if isinstance(x, (tuple, list)) else (x, x)
 
 
 @HEADS.register_module()

@@ -10,13 +10,12 @@ Two routes, same values:
   general  inside flags, the per-level count of inside anchors on the host (L236-250), index lists, `unmap`."""
 import torch
 
-from jdet_amd.models.boxes.anchor_target import anchor_inside_flags, dense_targets, images_to_levels
+from jdet_amd.models.boxes.anchor_target import anchor_inside_flags, dense_targets, targets_to_levels
 from jdet_amd.models.boxes.sampler import PseudoSampler
 from jdet_amd.utils.general import multi_apply, unmap
 from jdet_amd.utils.registry import BOXES, HEADS, build_from_cfg
 
 from .rotated_retina_head import RotatedRetinaHead
-from .s2anet_head import _cfg
 
 _ATSS_ASSIGN = dict(
     assigner=dict(type="ATSSAssignerRbbox", topk=9, iou_calculator=dict(type="BboxOverlaps2D_rotated")),
@@ -144,33 +143,5 @@ class RotatedATSSHead(RotatedRetinaHead):
             sampling=sampling, unmap_outputs=unmap_outputs)
         if any([labels is None for labels in all_labels]):
             return None
-        num_total_pos = sum([max(inds.numel(), 1) for inds in pos_inds_list])
-        num_total_neg = sum([max(inds.numel(), 1) for inds in neg_inds_list])
-        labels_list = images_to_levels(all_labels, num_level_anchors)
-        label_weights_list = images_to_levels(all_label_weights, num_level_anchors)
-        bbox_targets_list = images_to_levels(all_bbox_targets, num_level_anchors)
-        bbox_weights_list = images_to_levels(all_bbox_weights, num_level_anchors)
-        return (labels_list, label_weights_list, bbox_targets_list, bbox_weights_list, num_total_pos, num_total_neg)
-
-    def loss(self, cls_scores, bbox_preds, gt_bboxes, gt_labels, img_metas, gt_bboxes_ignore=None):
-        cfg = self.train_cfg.copy()
-        featmap_sizes = [tuple(featmap.shape[-2:]) for featmap in cls_scores]
-        assert len(featmap_sizes) == len(self.anchor_generators)
-        anchor_list, valid_flag_list = self.get_init_anchors(featmap_sizes, img_metas, cls_scores[0].device)
-        num_level_anchors = [anchors.size(0) for anchors in anchor_list[0]]
-        concat_anchor_list = [torch.cat(anchor_list[i]) for i in range(len(anchor_list))]
-        all_anchor_list = images_to_levels(concat_anchor_list, num_level_anchors)
-        label_channels = self.cls_out_channels if self.use_sigmoid_cls else 1
-        cls_reg_targets = self.anchor_target(anchor_list, valid_flag_list, gt_bboxes, img_metas, self.target_means,
-                                             self.target_stds, cfg, gt_bboxes_ignore_list=gt_bboxes_ignore,
-                                             gt_labels_list=gt_labels, label_channels=label_channels,
-                                             sampling=self.sampling)
-        if cls_reg_targets is None:
-            return None
-        labels_list, label_weights_list, bbox_targets_list, bbox_weights_list, num_total_pos, num_total_neg = \
-            cls_reg_targets
-        num_total_samples = num_total_pos + num_total_neg if self.sampling else num_total_pos
-        losses_cls, losses_bbox = multi_apply(self.loss_single, cls_scores, bbox_preds, all_anchor_list, labels_list,
-                                              label_weights_list, bbox_targets_list, bbox_weights_list,
-                                              num_total_samples=num_total_samples, cfg=cfg)
-        return dict(loss_cls=losses_cls, loss_bbox=losses_bbox)
+        return targets_to_levels((all_labels, all_label_weights, all_bbox_targets, all_bbox_weights), num_level_anchors,
+                                 pos_inds_list, neg_inds_list)

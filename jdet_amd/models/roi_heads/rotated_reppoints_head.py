@@ -25,27 +25,21 @@ import numpy as np
 import torch
 from torch import nn
 
-from jdet_amd.models.boxes.anchor_target import images_to_levels
+from jdet_amd.models.boxes.anchor_target import targets_to_levels
 from jdet_amd.models.boxes.assigner import (AssignResult, ConvexAssigner, MaxConvexIoUAssigner,
                                             assign_wrt_overlaps_device, stride_level_id)
-from jdet_amd.models.boxes.box_ops import rotated_box_to_poly
 from jdet_amd.models.boxes.sampler import PseudoSampler
 from jdet_amd.models.losses.convex_giou_loss import ConvexGIoULoss
 from jdet_amd.models.utils.modules import ConvModule
 from jdet_amd.models.utils.weight_init import bias_init_with_prob, normal_init
 from jdet_amd.ops.bbox_transforms import obb2poly, rectpoly2obb
 from jdet_amd.ops.dcn_v1 import DeformConv
-from jdet_amd.ops.nms_rotated import multiclass_nms_rotated
 from jdet_amd.ops.reppoints_min_area_bbox import reppoints_min_area_bbox
-from jdet_amd.utils.general import multi_apply, unmap
+from jdet_amd.utils.general import _pair, multi_apply, unmap
 from jdet_amd.utils.registry import BOXES, HEADS, LOSSES, build_from_cfg
 
-from .fcos_head import _device_counts
-from .s2anet_head import _cfg
-
-
-def _pair(x):
-    return tuple(x) if isinstance(x, (tuple, list)) else (x, x)
+from ._dense_head_common import (_cfg, cut_level, device_counts, merge_levels, nms_polys, pad_gts, parse_targets,
+                                 per_image)
 
 
 class MlvlPointGenerator:
@@ -353,23 +347,6 @@ class RotatedRepPointsHead(nn.Module):
         return proposals.is_cuda and proposals.dtype == torch.float32 and all(
             g.is_cuda and g.dtype == torch.float32 and g.dim() == 2 and g.shape[-1] == 5 for g in gt_bboxes_list)
 
-    @staticmethod
-    def _pad_gts(gt_polys_list, gt_labels_list):
-        """(gt (B, Kmax, 8), labels (B, Kmax) int32, counts: host list); Kmax >= 1, the rows beyond an image's count 0"""
-        B = len(gt_polys_list)
-        counts = [int(g.shape[0]) for g in gt_polys_list]
-        Kmax = max(max(counts), 1)
-        dev = gt_polys_list[0].device
-        if all(c == Kmax for c in counts):
-            return (torch.stack(gt_polys_list), torch.stack([t.to(torch.int32) for t in gt_labels_list]), counts)
-        gt = torch.zeros((B, Kmax, 8), dtype=torch.float32, device=dev)
-        gl = torch.zeros((B, Kmax), dtype=torch.int32, device=dev)
-        for b, (g, t) in enumerate(zip(gt_polys_list, gt_labels_list)):
-            if counts[b]:
-                gt[b, :counts[b]] = g
-                gl[b, :counts[b]] = t.to(torch.int32)
-        return gt, gl, counts
-
     def _dense_stage_targets(self, gt_inds, proposals, gt, gl, pos_weight):
         """the arrays _point_target_single builds from index lists, as `where` / `gather` over (B, N): gt_inds (B, N)
         int32 (-1 ignored, 0 negative, g + 1), proposals (N, D) | (B, N, D), gt (B, Kmax, 8), gl (B, Kmax) ->
@@ -396,13 +373,13 @@ class RotatedRepPointsHead(nn.Module):
         sets.  Returns the seven lists / counts of `get_targets` (the counts device tensors) + None."""
         num_level_proposals = [points.size(0) for points in proposals_list[0]]
         gt_polys = [obb2poly(g) for g in gt_bboxes_list]
-        gt, gl, counts = self._pad_gts(gt_polys, gt_labels_list)
+        gt, gl, counts = pad_gts(gt_polys, gt_labels_list, 8)
         B = len(gt_polys)
         if stage == "init":
             points = torch.cat(proposals_list[0])
             level_ids = [stride_level_id(s) for s in self.point_strides]
             gt_inds, _ = self.init_assigner.assign_batch(points, num_level_proposals, level_ids, gt, None,
-                                                         _device_counts(counts, points.device))
+                                                         device_counts(counts, points.device))
             proposals = points
             pos_weight = self.train_cfg.init.pos_weight
         else:
@@ -449,15 +426,8 @@ class RotatedRepPointsHead(nn.Module):
                                         unmap_outputs=unmap_outputs)
         if any([labels is None for labels in all_labels]):
             return None
-        num_total_pos = sum([max(inds.numel(), 1) for inds in pos_inds_list])
-        num_total_neg = sum([max(inds.numel(), 1) for inds in neg_inds_list])
-        labels_list = images_to_levels(all_labels, num_level_proposals)
-        label_weights_list = images_to_levels(all_label_weights, num_level_proposals)
-        bbox_gt_list = images_to_levels(all_bbox_gt, num_level_proposals)
-        proposals_list = images_to_levels(all_proposals, num_level_proposals)
-        proposal_weights_list = images_to_levels(all_proposal_weights, num_level_proposals)
-        return (labels_list, label_weights_list, bbox_gt_list, proposals_list, proposal_weights_list, num_total_pos,
-                num_total_neg, None)
+        return targets_to_levels((all_labels, all_label_weights, all_bbox_gt, all_proposals, all_proposal_weights),
+                                 num_level_proposals, pos_inds_list, neg_inds_list) + (None,)
 
     # ------------------------------------------------------------------------------------------------------------ loss
     def _cls_loss(self, cls_score, labels, label_weights, num_total_samples_refine):
@@ -575,72 +545,47 @@ class RotatedRepPointsHead(nn.Module):
     def get_bboxes(self, cls_scores, pts_preds_init, pts_preds_refine, img_metas, cfg=None, rescale=False,
                    with_nms=True, **kwargs):
         assert len(cls_scores) == len(pts_preds_refine)
-        num_levels = len(cls_scores)
-        featmap_sizes = [tuple(cls_scores[i].shape[-2:]) for i in range(num_levels)]
+        featmap_sizes = [tuple(cls_score.shape[-2:]) for cls_score in cls_scores]
         mlvl_priors = self.prior_generator.grid_priors(featmap_sizes, dtype=cls_scores[0].dtype,
                                                        device=cls_scores[0].device)
-        result_list = []
-        for img_id, img_meta in enumerate(img_metas):
-            cls_score_list = [cls_scores[i][img_id].detach() for i in range(num_levels)]
-            point_pred_list = [pts_preds_refine[i][img_id].detach() for i in range(num_levels)]
-            result_list.append(self._get_bboxes_single(cls_score_list, point_pred_list, mlvl_priors, img_meta, cfg,
-                                                       rescale, with_nms, **kwargs))
-        return result_list
+        return per_image(lambda b, cls_score_list, point_pred_list: self._get_bboxes_single(
+            cls_score_list, point_pred_list, mlvl_priors, img_metas[b], cfg, rescale, with_nms, **kwargs),
+            len(img_metas), cls_scores, pts_preds_refine)
+
+    def _level_scores(self, cls_score):
+        """a level's (C, H, W) map -> (scores, rank); rank() is the score the `nms_pre` cut ranks the rows by.  Softmax:
+        the scores lose their LAST column and the ranking leaves out the first one as well (the reference's rule,
+        kept)"""
+        cls_score = cls_score.permute(1, 2, 0).reshape(-1, self.cls_out_channels)
+        if self.use_sigmoid_cls:
+            scores = cls_score.sigmoid()
+            return scores, lambda: scores.max(dim=1).values
+        scores = cls_score.softmax(-1)[:, :-1]
+        return scores, lambda: scores[:, 1:].max(dim=1).values
 
     def _get_bboxes_single(self, cls_score_list, point_pred_list, mlvl_priors, img_meta, cfg, rescale=False,
                            with_nms=True, **kwargs):
         cfg = self.test_cfg if cfg is None else cfg
         assert len(cls_score_list) == len(point_pred_list)
-        scale_factor = img_meta["scale_factor"]
         mlvl_bboxes = []
         mlvl_scores = []
         for level_idx, (cls_score, points_pred, points) in enumerate(zip(cls_score_list, point_pred_list, mlvl_priors)):
             assert cls_score.shape[-2:] == points_pred.shape[-2:]
-            cls_score = cls_score.permute(1, 2, 0).reshape(-1, self.cls_out_channels)
-            if self.use_sigmoid_cls:
-                scores = cls_score.sigmoid()
-            else:
-                scores = cls_score.softmax(-1)[:, :-1]
+            scores, rank = self._level_scores(cls_score)
             points_pred = points_pred.permute(1, 2, 0).reshape(-1, 2 * self.num_points)
-            nms_pre = cfg.get("nms_pre", -1)
-            if 0 < nms_pre < scores.shape[0]:
-                if self.use_sigmoid_cls:
-                    max_scores = scores.max(dim=1).values
-                else:
-                    max_scores = scores[:, 1:].max(dim=1).values
-                _, topk_inds = max_scores.topk(nms_pre)
-                points = points[topk_inds, :]
-                points_pred = points_pred[topk_inds, :]
-                scores = scores[topk_inds, :]
+            points, points_pred, scores = cut_level(cfg.get("nms_pre", -1), rank, points, points_pred, scores)
             poly_pred = self.points2rotrect(points_pred, y_first=True)
             bbox_pos_center = points[:, :2].repeat(1, 4)
             polys = poly_pred * self.point_strides[level_idx] + bbox_pos_center
             mlvl_bboxes.append(rectpoly2obb(polys))
             mlvl_scores.append(scores)
-        mlvl_bboxes = torch.cat(mlvl_bboxes)
-        if rescale:
-            mlvl_bboxes = torch.cat([mlvl_bboxes[..., :4] / scale_factor, mlvl_bboxes[..., 4:]], dim=-1)
-        mlvl_scores = torch.cat(mlvl_scores)
-        if self.use_sigmoid_cls:
-            padding = mlvl_scores.new_zeros((mlvl_scores.shape[0], 1))
-            mlvl_scores = torch.cat([padding, mlvl_scores], dim=1)
+        merged = merge_levels(mlvl_bboxes, mlvl_scores, img_meta["scale_factor"], rescale, self.use_sigmoid_cls)
         if not with_nms:
             raise NotImplementedError
-        det_bboxes, det_labels = multiclass_nms_rotated(mlvl_bboxes, mlvl_scores, cfg.score_thr, cfg.nms,
-                                                        cfg.max_per_img)
-        boxes = det_bboxes[:, :5]
-        scores = det_bboxes[:, 5]
-        return rotated_box_to_poly(boxes), scores, det_labels
+        return nms_polys(*merged, cfg)
 
     def parse_targets(self, targets):
-        img_metas, gt_bboxes, gt_bboxes_ignore, gt_labels = [], [], [], []
-        for target in targets:
-            if self.training:
-                gt_bboxes.append(target["rboxes"])
-                gt_labels.append(target["labels"])
-                gt_bboxes_ignore.append(target["rboxes_ignore"])
-            img_metas.append(dict(img_shape=target["img_size"][::-1], scale_factor=target["scale_factor"],
-                                  pad_shape=target["pad_shape"]))
+        gt_bboxes, gt_labels, img_metas, gt_bboxes_ignore = parse_targets(targets, self.training)
         if not self.training:
             return dict(img_metas=img_metas)
         return dict(gt_bboxes=gt_bboxes, gt_labels=gt_labels, img_metas=img_metas, gt_bboxes_ignore=gt_bboxes_ignore)

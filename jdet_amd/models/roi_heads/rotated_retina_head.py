@@ -1,20 +1,17 @@
 """RetinaNet-OBB head.  Mirrors python/jdet/models/roi_heads/rotated_retina_head.py:L13-398: 4+4 stacked 3x3
 conv towers, 9 rotated anchors per location (3 ratios x 3 octave scales, angle 0), focal + L1/SmoothL1
 loss on DeltaXYWHABBoxCoder targets, top-k -> decode -> multiclass rotated NMS at test time."""
-import torch
 from torch import nn
 
 from jdet_amd.ops.conv_igemm import conv_module
 from jdet_amd.models.boxes.anchor_generator import AnchorGeneratorRotatedRetinaNet
-from jdet_amd.models.boxes.anchor_target import anchor_target, images_to_levels
 from jdet_amd.models.utils.level_pack import run_levels
 from jdet_amd.models.utils.modules import ConvModule
 from jdet_amd.models.utils.weight_init import bias_init_with_prob, normal_init
-from jdet_amd.utils.general import multi_apply
 from jdet_amd.utils.registry import HEADS, LOSSES, build_from_cfg
 
 from ._anchor_head_common import RotatedAnchorHeadMixin
-from .s2anet_head import _DEFAULT_ASSIGN, _cfg
+from ._dense_head_common import _DEFAULT_ASSIGN, _cfg
 
 
 @HEADS.register_module()
@@ -89,46 +86,18 @@ class RotatedRetinaHead(RotatedAnchorHeadMixin, nn.Module):
         return conv_module(self.retina_cls, cls_feat), conv_module(self.retina_reg, reg_feat)
 
     def loss(self, cls_scores, bbox_preds, gt_bboxes, gt_labels, img_metas, gt_bboxes_ignore=None):
-        cfg = self.train_cfg.copy()
         featmap_sizes = [tuple(featmap.shape[-2:]) for featmap in cls_scores]
         assert len(featmap_sizes) == len(self.anchor_generators)
         anchor_list, valid_flag_list = self.get_init_anchors(featmap_sizes, img_metas, cls_scores[0].device)
-        num_level_anchors = [anchors.size(0) for anchors in anchor_list[0]]
-        concat_anchor_list = [torch.cat(anchor_list[i]) for i in range(len(anchor_list))]
-        all_anchor_list = images_to_levels(concat_anchor_list, num_level_anchors)
-        label_channels = self.cls_out_channels if self.use_sigmoid_cls else 1
-        cls_reg_targets = anchor_target(anchor_list, valid_flag_list, gt_bboxes, img_metas, self.target_means,
-                                        self.target_stds, cfg, gt_bboxes_ignore_list=gt_bboxes_ignore,
-                                        gt_labels_list=gt_labels, label_channels=label_channels, sampling=self.sampling)
-        if cls_reg_targets is None:
-            return None
-        labels_list, label_weights_list, bbox_targets_list, bbox_weights_list, num_total_pos, num_total_neg = \
-            cls_reg_targets
-        num_total_samples = num_total_pos + num_total_neg if self.sampling else num_total_pos
-        losses_cls, losses_bbox = multi_apply(self.loss_single, cls_scores, bbox_preds, all_anchor_list, labels_list,
-                                              label_weights_list, bbox_targets_list, bbox_weights_list,
-                                              num_total_samples=num_total_samples, cfg=cfg)
-        return dict(loss_cls=losses_cls, loss_bbox=losses_bbox)
-
-    def loss_single(self, cls_score, bbox_pred, anchors, labels, label_weights, bbox_targets, bbox_weights,
-                    num_total_samples, cfg):
-        return self._loss_single(self.loss_cls, self.loss_bbox, cls_score, bbox_pred, anchors, labels, label_weights,
-                                 bbox_targets, bbox_weights, num_total_samples, cfg)
+        losses = self._stage_loss(cls_scores, bbox_preds, anchor_list, valid_flag_list, gt_bboxes, gt_labels, img_metas,
+                                  gt_bboxes_ignore, self.train_cfg.copy(), self.loss_cls, self.loss_bbox)
+        return None if losses is None else dict(loss_cls=losses[0], loss_bbox=losses[1])
 
     def get_bboxes(self, cls_scores, bbox_preds, img_metas, rescale=True):
         assert len(cls_scores) == len(bbox_preds)
-        cfg = self.test_cfg.copy()
         featmap_sizes = [tuple(featmap.shape[-2:]) for featmap in cls_scores]
-        num_levels = len(cls_scores)
         anchor_list, _ = self.get_init_anchors(featmap_sizes, img_metas, cls_scores[0].device)
-        result_list = []
-        for img_id in range(len(img_metas)):
-            cls_score_list = [cls_scores[i][img_id].detach() for i in range(num_levels)]
-            bbox_pred_list = [bbox_preds[i][img_id].detach() for i in range(num_levels)]
-            result_list.append(self.get_bboxes_single(cls_score_list, bbox_pred_list, anchor_list[img_id],
-                                                      img_metas[img_id]["img_shape"],
-                                                      img_metas[img_id]["scale_factor"], cfg, rescale))
-        return result_list
+        return self._get_bboxes(cls_scores, bbox_preds, anchor_list, img_metas, rescale)
 
     def forward(self, feats, targets):
         per_level = run_levels(list(feats), lambda x, mask: self.forward_single(x, mask=mask))

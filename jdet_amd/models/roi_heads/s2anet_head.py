@@ -16,7 +16,7 @@ except ImportError:      # pragma: no cover
     _reparametrize_module = None
 
 from jdet_amd.models.boxes.anchor_generator import AnchorGeneratorRotatedS2ANet
-from jdet_amd.models.boxes.anchor_target import anchor_target, images_to_levels
+from jdet_amd.models.boxes.anchor_target import anchor_target
 from jdet_amd.models.boxes.box_ops import delta2bbox_rotated
 from jdet_amd.models.utils.level_pack import LevelPack
 
@@ -39,34 +39,10 @@ from jdet_amd.ops.conv_igemm import conv_module
 from jdet_amd.models.utils.weight_init import bias_init_with_prob, normal_init
 from jdet_amd.ops.dcn_v1 import DeformConv
 from jdet_amd.ops.orn import ORConv2d, RotationInvariantPooling
-from jdet_amd.utils.general import multi_apply
 from jdet_amd.utils.registry import HEADS, LOSSES, build_from_cfg
 
 from ._anchor_head_common import RotatedAnchorHeadMixin
-
-
-class _AttrDict(dict):
-    """dict with Config-like attribute access (missing -> None), for the default train/test cfgs"""
-
-    def __getattr__(self, name):
-        return self.get(name)
-
-    def copy(self):
-        return _AttrDict(self)
-
-
-def _cfg(d):
-    if type(d) is dict:  # plain dicts (the signature defaults); Config objects already have attribute access
-        return _AttrDict({k: _cfg(v) if isinstance(v, dict) else v for k, v in d.items()})
-    return d
-
-
-_DEFAULT_ASSIGN = dict(
-    assigner=dict(type="MaxIoUAssigner", pos_iou_thr=0.5, neg_iou_thr=0.4, min_pos_iou=0, ignore_iof_thr=-1,
-                  iou_calculator=dict(type="BboxOverlaps2D_rotated")),
-    bbox_coder=dict(type="DeltaXYWHABBoxCoder", target_means=(0., 0., 0., 0., 0.), target_stds=(1., 1., 1., 1., 1.),
-                    clip_border=True),
-    allowed_border=-1, pos_weight=-1, debug=False)
+from ._dense_head_common import _DEFAULT_ASSIGN, _AttrDict, _cfg  # noqa: F401  (re-exported: existing imports)
 
 
 @HEADS.register_module()
@@ -254,80 +230,28 @@ class S2ANetHead(RotatedAnchorHeadMixin, nn.Module):
         featmap_sizes = [tuple(featmap.shape[-2:]) for featmap in odm_cls_scores]
         assert len(featmap_sizes) == len(self.anchor_generators)
         device = odm_cls_scores[0].device
-        anchor_list, valid_flag_list = self.get_init_anchors(featmap_sizes, img_metas, device)
-        num_level_anchors = [anchors.size(0) for anchors in anchor_list[0]]
         # per-level anchors are only read by the loss when it regresses decoded boxes
         need_anchors = cfg.fam_cfg.get("reg_decoded_bbox", False) or cfg.odm_cfg.get("reg_decoded_bbox", False)
-        all_anchor_list = [None] * len(num_level_anchors)
-        if need_anchors:
-            concat_anchor_list = [torch.cat(anchor_list[i]) for i in range(len(anchor_list))]
-            all_anchor_list = images_to_levels(concat_anchor_list, num_level_anchors)
-
-        label_channels = self.cls_out_channels if self.use_sigmoid_cls else 1
-        cls_reg_targets = anchor_target(anchor_list, valid_flag_list, gt_bboxes, img_metas, self.target_means,
-                                        self.target_stds, cfg.fam_cfg, gt_bboxes_ignore_list=gt_bboxes_ignore,
-                                        gt_labels_list=gt_labels, label_channels=label_channels,
-                                        sampling=self.sampling)
-        if cls_reg_targets is None:
+        gts = (gt_bboxes, gt_labels, img_metas, gt_bboxes_ignore)
+        fam = self._stage_loss(fam_cls_scores, fam_bbox_preds, *self.get_init_anchors(featmap_sizes, img_metas, device),
+                               *gts, cfg.fam_cfg, self.loss_fam_cls, self.loss_fam_bbox, need_anchors=need_anchors)
+        if fam is None:
             return None
-        labels_list, label_weights_list, bbox_targets_list, bbox_weights_list, num_total_pos, num_total_neg = \
-            cls_reg_targets
-        num_total_samples = num_total_pos + num_total_neg if self.sampling else num_total_pos
-        losses_fam_cls, losses_fam_bbox = multi_apply(
-            self.loss_fam_single, fam_cls_scores, fam_bbox_preds, all_anchor_list, labels_list, label_weights_list,
-            bbox_targets_list, bbox_weights_list, num_total_samples=num_total_samples, cfg=cfg.fam_cfg)
-
-        refine_anchors_list, valid_flag_list = self.get_refine_anchors(featmap_sizes, refine_anchors, img_metas,
-                                                                       device=device)
-        num_level_anchors = [anchors.size(0) for anchors in refine_anchors_list[0]]
-        all_anchor_list = [None] * len(num_level_anchors)
-        if need_anchors:
-            concat_anchor_list = [torch.cat(refine_anchors_list[i]) for i in range(len(refine_anchors_list))]
-            all_anchor_list = images_to_levels(concat_anchor_list, num_level_anchors)
-        cls_reg_targets = odm_targets
-        if cls_reg_targets is None:
-            cls_reg_targets = anchor_target(refine_anchors_list, valid_flag_list, gt_bboxes, img_metas,
-                                            self.target_means, self.target_stds, cfg.odm_cfg,
-                                            gt_bboxes_ignore_list=gt_bboxes_ignore, gt_labels_list=gt_labels,
-                                            label_channels=label_channels, sampling=self.sampling)
-        if cls_reg_targets is None:
+        odm = self._stage_loss(odm_cls_scores, odm_bbox_preds,
+                               *self.get_refine_anchors(featmap_sizes, refine_anchors, img_metas, device=device),
+                               *gts, cfg.odm_cfg, self.loss_odm_cls, self.loss_odm_bbox, targets=odm_targets,
+                               need_anchors=need_anchors)
+        if odm is None:
             return None
-        (labels_list, label_weights_list, bbox_targets_list, bbox_weights_list, num_total_pos, num_total_neg) = \
-            cls_reg_targets
-        num_total_samples = num_total_pos + num_total_neg if self.sampling else num_total_pos
-        losses_odm_cls, losses_odm_bbox = multi_apply(
-            self.loss_odm_single, odm_cls_scores, odm_bbox_preds, all_anchor_list, labels_list, label_weights_list,
-            bbox_targets_list, bbox_weights_list, num_total_samples=num_total_samples, cfg=cfg.odm_cfg)
-        return dict(loss_fam_cls=losses_fam_cls, loss_fam_bbox=losses_fam_bbox, loss_odm_cls=losses_odm_cls,
-                    loss_odm_bbox=losses_odm_bbox)
-
-    def loss_fam_single(self, fam_cls_score, fam_bbox_pred, anchors, labels, label_weights, bbox_targets,
-                        bbox_weights, num_total_samples, cfg):
-        return self._loss_single(self.loss_fam_cls, self.loss_fam_bbox, fam_cls_score, fam_bbox_pred, anchors, labels,
-                                 label_weights, bbox_targets, bbox_weights, num_total_samples, cfg)
-
-    def loss_odm_single(self, odm_cls_score, odm_bbox_pred, anchors, labels, label_weights, bbox_targets,
-                        bbox_weights, num_total_samples, cfg):
-        return self._loss_single(self.loss_odm_cls, self.loss_odm_bbox, odm_cls_score, odm_bbox_pred, anchors, labels,
-                                 label_weights, bbox_targets, bbox_weights, num_total_samples, cfg)
+        return dict(loss_fam_cls=fam[0], loss_fam_bbox=fam[1], loss_odm_cls=odm[0], loss_odm_bbox=odm[1])
 
     # ------------------------------------------------------------------ inference
     def get_bboxes(self, fam_cls_scores, fam_bbox_preds, refine_anchors, odm_cls_scores, odm_bbox_preds, img_metas,
                    rescale=True):
         assert len(odm_cls_scores) == len(odm_bbox_preds)
-        cfg = self.test_cfg.copy()
         featmap_sizes = [tuple(featmap.shape[-2:]) for featmap in odm_cls_scores]
-        num_levels = len(odm_cls_scores)
-        refine_anchors = self.get_refine_anchors(featmap_sizes, refine_anchors, img_metas, is_train=False)
-        result_list = []
-        for img_id in range(len(img_metas)):
-            cls_score_list = [odm_cls_scores[i][img_id].detach() for i in range(num_levels)]
-            bbox_pred_list = [odm_bbox_preds[i][img_id].detach() for i in range(num_levels)]
-            img_shape = img_metas[img_id]["img_shape"]
-            scale_factor = img_metas[img_id]["scale_factor"]
-            result_list.append(self.get_bboxes_single(cls_score_list, bbox_pred_list, refine_anchors[0][img_id],
-                                                      img_shape, scale_factor, cfg, rescale))
-        return result_list
+        refine_anchors, _ = self.get_refine_anchors(featmap_sizes, refine_anchors, img_metas, is_train=False)
+        return self._get_bboxes(odm_cls_scores, odm_bbox_preds, refine_anchors, img_metas, rescale)
 
     def _level_outputs(self, feats):
         """per level (fam_cls_score, fam_bbox_pred, refine_anchor, odm_cls_score, odm_bbox_pred); the small levels

@@ -2,12 +2,9 @@
 import torch
 
 from .. import _lib as L
+from ..utils.general import _pair
 
 V_ROT, V_ROT_V1, V_RI, V_HBB0, V_HBB1 = 0, 1, 2, 3, 4
-
-
-def _pair(x):
-    return tuple(x) if isinstance(x, (tuple, list)) else (x, x)
 
 
 def to_nhwc(x):

@@ -25,12 +25,9 @@ import torch.nn.functional as F
 from torch import nn
 
 from .. import _lib as L
+from ..utils.general import _pair
 
 __all__ = ["DeformConv", "deform_conv", "DeformConvFunction"]
-
-
-def _pair(x):
-    return tuple(x) if isinstance(x, (tuple, list)) else (x, x)
 
 
 def _out_hw(H, W, kh, kw, pad, stride, dil):

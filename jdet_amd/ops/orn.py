@@ -11,13 +11,10 @@ import torch.nn.functional as F
 from torch import nn
 
 from .. import _lib as L
+from ..utils.general import _pair
 from . import conv_igemm
 
 __all__ = ["ORConv2d", "RotationInvariantPooling", "active_rotating_filter", "arf_forward", "arf_backward"]
-
-
-def _pair(x):
-    return tuple(x) if isinstance(x, (tuple, list)) else (x, x)
 
 
 def arf_forward(input, indices):
