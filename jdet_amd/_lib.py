@@ -199,6 +199,15 @@ H2RBOX_SIGNATURES = {
                                            _p, _p, _p, _p, _p]),
 }
 
+# include/jdet_hip_ld.h (csrc/dist_loss.hip; same library, a table of its own for the reason ATSS_SIGNATURES has one;
+# tests/test_ld_cpu.py checks it against the header and the exports)
+LD_SIGNATURES = {
+    "jdet_dist_integral": (_i, [_p, _l, _i, _f, _f, _f, _f, _p, _p]),
+    "jdet_dist_bbox_loss_level": (_i, [_p, _p, _l, _l, _p, _l, _l, _l, _i, _f, _f, _f, _f, _f, _p, _f, _p, _p, _p, _sz, _p]),
+    "jdet_kd_kl_div_level_forward": (_i, [_p, _p, _p, _l, _l, _l, _i, _f, _f, _p, _p, _p, _sz, _p]),
+    "jdet_kd_kl_div_level_backward": (_i, [_p, _p, _p, _l, _l, _l, _i, _f, _f, _p, _p, _p, _p]),
+}
+
 _lib = None
 
 # Hull-point ordering inside the rotated IoU: 0 = the reference's CPU path (std::sort,
@@ -231,7 +240,7 @@ def lib():
         l = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in list(SIGNATURES.items()) + list(ATSS_SIGNATURES.items()) + list(ROWS_SIGNATURES.items()) + \
                 list(ROWS_FWD_SIGNATURES.items()) + list(FCOS_SIGNATURES.items()) + list(REPPOINTS_SIGNATURES.items()) + \
-                list(H2RBOX_SIGNATURES.items()):
+                list(H2RBOX_SIGNATURES.items()) + list(LD_SIGNATURES.items()):
             fn = getattr(l, name)  # AttributeError here == ABI drift: fail loudly
             fn.restype = res
             fn.argtypes = args

@@ -298,3 +298,49 @@ GLIDING_CFG = dict(
             pos_weight=-1, reg_class_agnostic=False, ratio_thr=0.8, max_per_img=2000)),
     optimizer=dict(type="SGD", lr=0.005, momentum=0.9, weight_decay=0.0001, grad_clip=dict(max_norm=35, norm_type=2)),
     scheduler=dict(type="StepLR", warmup="linear", warmup_iters=500, warmup_ratio=0.001, milestones=[7, 10]))
+
+
+# ---- localization distillation (configs/ld/): an R18 RetinaNet-OBB, the same with distribution heads on R18 / R50, and
+# the R50 -> R18 distillation recipe.  tests/golden/configs/*_ld_*.yaml / rotated_retinanet_obb_*r18*.yaml hold the
+# model sections as `Config` reads them.
+def _ld_retinanet_cfg(head_type, backbone="Resnet18", **head):
+    in_channels = [64, 128, 256, 512] if backbone == "Resnet18" else [256, 512, 1024, 2048]
+    return dict(
+        model=dict(
+            type="RotatedRetinaNet",
+            backbone=dict(type=backbone, frozen_stages=1, return_stages=["layer1", "layer2", "layer3", "layer4"],
+                          pretrained=True),
+            neck=dict(type="FPN", in_channels=in_channels, out_channels=256, start_level=1, add_extra_convs="on_input",
+                      num_outs=5),
+            bbox_head=dict(
+                type=head_type, num_classes=16, in_channels=256, feat_channels=256, stacked_convs=4,
+                octave_base_scale=4, scales_per_octave=3, anchor_ratios=[1.0, 0.5, 2.0],
+                anchor_strides=[8, 16, 32, 64, 128], target_means=[.0, .0, .0, .0, .0],
+                target_stds=[1.0, 1.0, 1.0, 1.0, 1.0],
+                loss_cls=dict(type="FocalLoss", use_sigmoid=True, gamma=2.0, alpha=0.25, loss_weight=1.0),
+                loss_bbox=dict(type="L1Loss", loss_weight=1.0), **head,
+                test_cfg=dict(nms_pre=2000, min_bbox_size=0, score_thr=0.05, nms=dict(type="nms_rotated", iou_thr=0.1),
+                              max_per_img=2000),
+                train_cfg=dict(
+                    assigner=dict(type="MaxIoUAssigner", pos_iou_thr=0.5, neg_iou_thr=0.4, min_pos_iou=0,
+                                  ignore_iof_thr=-1, iou_calculator=dict(type="BboxOverlaps2D_rotated")),
+                    bbox_coder=dict(type="DeltaXYWHABBoxCoder", target_means=(0., 0., 0., 0., 0.),
+                                    target_stds=(1., 1., 1., 1., 1.), clip_border=True),
+                    allowed_border=-1, pos_weight=-1, debug=False))),
+        **_SGD_1X)
+
+
+# configs/ld/rotated_retinanet_obb_r18_fpn_1x_dota.py
+RETINANET_R18_CFG = _ld_retinanet_cfg("RotatedRetinaHead")
+# configs/ld/rotated_retinanet_obb_distribution_r18_fpn_1x_dota.py, ..._r50_fpn_1x_dota.py (reg_max: the head's default, 8)
+DIST_RETINANET_R18_CFG = _ld_retinanet_cfg("RotatedRetinaDistributionHead")
+DIST_RETINANET_R50_CFG = _ld_retinanet_cfg("RotatedRetinaDistributionHead", backbone="Resnet50")
+# configs/ld/ld_rotated_retinanet_obb_r18_r50_fpn_1x_dota.py.  teacher_config: the R50 config above instead of its file
+# name; teacher_ckpt: None instead of the file's https link -- pass a local checkpoint of the teacher to distil from
+LD_RETINANET_CFG = _ld_retinanet_cfg(
+    "RotatedRetinaLocalizationDistillationHead",
+    loss_ld=dict(type="KnowledgeDistillationKLDivLoss", loss_weight=10, T=10),
+    loss_kd=dict(type="KnowledgeDistillationKLDivLoss", loss_weight=10, T=2),
+    loss_im=dict(type="IMLoss", loss_weight=0), imitation_method="finegrained", reg_max=8)
+LD_RETINANET_CFG["model"] = dict(LD_RETINANET_CFG["model"], type="KnowledgeDistillationSingleStageDetector",
+                                 teacher_config=DIST_RETINANET_R50_CFG, teacher_ckpt=None)

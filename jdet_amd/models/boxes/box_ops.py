@@ -147,3 +147,47 @@ def distance2obb(points, distance, max_shape=None):
     offset = torch.bmm(Matrix, offset_t).squeeze(2)
     ctr = points + offset
     return regular_obb(torch.cat([ctr, wh, theta], dim=1))
+
+
+# ---- the discretised regression distributions of the localization-distillation heads (box_ops.py:L709-723) ------------
+DIST_ENDS = (-2.0, 2.0)            # the bins of the four box sides span [-2, 2]
+DIST_ANGLE_ENDS = (-5.0, 2.0)      # those of the angle [-5, 2]
+
+
+def _dist_bins(n, ends, like):
+    """e_k = lo + k * ((hi - lo) / n), k = 0 .. n, evaluated in x's dtype (exact in fp32 at n = 8)"""
+    lo, hi = ends
+    step = torch.tensor((hi - lo), dtype=like.dtype, device=like.device) / n
+    return lo + torch.arange(n + 1, dtype=like.dtype, device=like.device) * step
+
+
+def _integral(x, n, ends):
+    # softmax(x) . e as (exp(x - max) . e) / sum exp(x - max): one division per row, so a constant row gives exactly the
+    # bins' mean and a saturated one exactly its bin (the kernel's form, csrc/dist_loss.hip)
+    y = x.reshape(-1, n + 1)
+    y = torch.exp(y - y.max(dim=1, keepdim=True).values.detach())
+    return (y * _dist_bins(n, ends, y)).sum(dim=1) / y.sum(dim=1)
+
+
+def integral(x, n):
+    """(rows, 4 * (n + 1)) logits -> (rows, 4): the expectation of each side's distribution over bins on [-2, 2]"""
+    return _integral(x, n, DIST_ENDS).reshape(-1, 4)
+
+
+def integral_angle(x, n):
+    """(rows, n + 1) logits -> (rows,): the same for the angle, bins on [-5, 2]"""
+    return _integral(x, n, DIST_ANGLE_ENDS).reshape(-1)
+
+
+def integral_rows(x, n):
+    """(rows, 5 * (n + 1)) logits of a distribution head -> (rows, 5) deltas [integral of the four sides, integral_angle].
+    fp32 on the device without a gradient: one launch (jdet_dist_integral); otherwise composed from the two above."""
+    k = n + 1
+    if (x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.shape[1] == 5 * k and k <= 32 and
+            not (torch.is_grad_enabled() and x.requires_grad) and not torch.is_autocast_enabled()):
+        x = x.contiguous()
+        out = torch.empty((x.shape[0], 5), dtype=torch.float32, device=x.device)
+        L.check(L.lib().jdet_dist_integral(L.ptr(x), x.shape[0], n, *DIST_ENDS, *DIST_ANGLE_ENDS, L.ptr(out),
+                                           L.stream_ptr(x)), "jdet_dist_integral")
+        return out
+    return torch.cat([integral(x[:, :4 * k], n), integral_angle(x[:, 4 * k:], n)[:, None]], dim=1)

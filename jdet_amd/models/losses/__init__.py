@@ -7,3 +7,4 @@ from .poly_iou_loss import PolyIoULoss, poly_iou_loss  # noqa: F401
 from .convex_giou_loss import ConvexGIoULoss  # noqa: F401
 from .iou_loss import IoULoss, iou_loss  # noqa: F401
 from .h2rbox_loss import H2RBoxLoss  # noqa: F401
+from .kd_loss import IMLoss, KnowledgeDistillationKLDivLoss  # noqa: F401

@@ -70,7 +70,9 @@ class Runner:
         if channels_last:
             # 4-D conv weights only (ORConv2d keeps a 5-D ARF weight; nn.Module.to(memory_format=) would
             # try to convert it as a 3-D-conv weight and fail)
-            for p in self.model.parameters():
+            # (frozen_parameters: a distillation teacher, which is outside parameters(); networks/kd_one_stage.py)
+            frozen = self.model.frozen_parameters() if hasattr(self.model, "frozen_parameters") else []
+            for p in list(self.model.parameters()) + list(frozen):
                 # 1x1 kernels are already both layouts; leaving their strides alone keeps them equal to the
                 # strides of the gradients MIOpen returns (DDP's bucket views otherwise copy)
                 if p.dim() == 4 and p.shape[2] * p.shape[3] > 1:
