@@ -208,6 +208,13 @@ LD_SIGNATURES = {
     "jdet_kd_kl_div_level_backward": (_i, [_p, _p, _p, _l, _l, _l, _i, _f, _f, _p, _p, _p, _p]),
 }
 
+# include/jdet_hip_bf16x3.h (csrc/conv_bf16x3.hip; same library, a table of its own for the reason ROWS_FWD_SIGNATURES has
+# one; tests/test_conv_bf16x3_cpu.py checks it against the header and the exports)
+BF16X3_SIGNATURES = {
+    "jdet_conv3x3_bf16x3_supported": (_i, [_i, _i]),
+    "jdet_conv3x3_bf16x3_forward": (_i, [_p, _i, _i, _i, _i, _p, _i, _p, _i, _p, _p, _p]),
+}
+
 _lib = None
 
 # Hull-point ordering inside the rotated IoU: 0 = the reference's CPU path (std::sort,
@@ -240,7 +247,7 @@ def lib():
         l = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in list(SIGNATURES.items()) + list(ATSS_SIGNATURES.items()) + list(ROWS_SIGNATURES.items()) + \
                 list(ROWS_FWD_SIGNATURES.items()) + list(FCOS_SIGNATURES.items()) + list(REPPOINTS_SIGNATURES.items()) + \
-                list(H2RBOX_SIGNATURES.items()) + list(LD_SIGNATURES.items()):
+                list(H2RBOX_SIGNATURES.items()) + list(LD_SIGNATURES.items()) + list(BF16X3_SIGNATURES.items()):
             fn = getattr(l, name)  # AttributeError here == ABI drift: fail loudly
             fn.restype = res
             fn.argtypes = args

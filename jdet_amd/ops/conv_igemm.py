@@ -11,6 +11,10 @@ deformable conv keeps the column matrix, which its weight-gradient GEMM reads.
 Measured on MI355X, 256 -> 256 channels, batch 2 (scripts/conv_igemm_timing.py, profiles/r03_conv_igemm.md):
 128^2 map 296 us (130.6 TFLOP/s, MFMA busy 80.8 %) vs 394 us for library conv + bias + ReLU; 64^2 map 86-94 vs 126 us;
 32^2 / 16^2 / 8^2 maps 37 / 18 / 16 us vs 55 / 29 / 26 us (K steps split over workgroups through a scratch buffer).
+
+The big shapes (at least 512 tiles of 128 x 128, Cin % 32 == 0: the P3 layers of the 1024^2 step) go to
+csrc/conv_bf16x3.hip instead: the same convolution on the bf16 matrix pipe through an exact three-way split of the fp32
+operands, as accurate as the fp32 kernel; see BF16X3 below and profiles/conv_bf16x3.md.
 """
 import os
 import weakref
@@ -29,8 +33,49 @@ def weight_krsc(weight):
     return L.f32c(weight.permute(0, 2, 3, 1))
 
 
-def conv3x3_nhwc(x_nhwc, w_krsc, bias=None, relu=False, rowmask=None, offset=None, tile=0):
-    """x_nhwc (N,H,W,Cin) contiguous fp32, w_krsc (Cout,3,3,Cin), offset (N,18,H,W) or None -> (N,H,W,Cout)"""
+# The big dense layers on the bf16 matrix pipe through an exact three-way split of the fp32 operands (csrc/conv_bf16x3.hip,
+# profiles/conv_bf16x3.md): the shapes the fp32 kernel gives its 128 x 128 tile (at least 512 of them) with Cin % 32 == 0,
+# automatic tile, plain form -- with and without gradients alike (one kernel per shape: the no-grad route of a layer
+# computes what its training forward computes).  JDET_CONV_BF16X3 switches the forward route, JDET_CONV_BF16X3_DGRAD the
+# data gradient of the same layers (grad_x = this kernel on the flipped weights, in place of the library's); the defaults
+# follow the step pairs of profiles/conv_bf16x3.md.
+BF16X3 = os.environ.get("JDET_CONV_BF16X3", "1") == "1"
+BF16X3_DGRAD = os.environ.get("JDET_CONV_BF16X3_DGRAD", "1") == "1"
+
+
+def bf16x3_supported(cin, cout):
+    return bool(L.lib().jdet_conv3x3_bf16x3_supported(int(cin), int(cout)))
+
+
+def bf16x3_big(positions, cin, cout):
+    """the shapes the split kernel is routed to: conv_igemm.hip's `big` rule (128 x 128 tiles >= 512), channels it takes"""
+    # (plain integer tests first: every fused 3x3 call of every model passes here, most of them below the rule)
+    if ((positions + 127) // 128) * ((cout + 127) // 128) < 512 or cin % 32 != 0 or positions * max(cin, cout) >= 2 ** 30:
+        return False
+    return bf16x3_supported(cin, cout)
+
+
+def conv3x3_bf16x3_nhwc(x_nhwc, w_krsc, bias=None, relu=False, rowmask=None):
+    """x_nhwc (N,H,W,Cin) contiguous fp32, w_krsc (Cout,3,3,Cin) -> (N,H,W,Cout) by jdet_conv3x3_bf16x3_forward (any
+    shape it supports; `conv3x3_nhwc` routes the big ones here)"""
+    L.need_device(x_nhwc, w_krsc, bias, rowmask)
+    N, H, W, Cin = x_nhwc.shape
+    Cout = w_krsc.shape[0]
+    if w_krsc.shape[1:] != (3, 3, Cin):
+        raise ValueError("weight %r does not match input channels %d" % (tuple(w_krsc.shape), Cin))
+    x_nhwc, w_krsc = L.f32c(x_nhwc), L.f32c(w_krsc)
+    y = torch.empty((N, H, W, Cout), dtype=torch.float32, device=x_nhwc.device)
+    L.check(L.lib().jdet_conv3x3_bf16x3_forward(
+        L.ptr(x_nhwc), N, H, W, Cin, L.ptr(w_krsc), Cout, L.ptr(L.f32c(bias)) if bias is not None else None,
+        int(bool(relu)), L.ptr(L.f32c(rowmask)) if rowmask is not None else None, L.ptr(y), L.stream_ptr(x_nhwc)),
+        "jdet_conv3x3_bf16x3_forward")
+    return y
+
+
+def conv3x3_nhwc(x_nhwc, w_krsc, bias=None, relu=False, rowmask=None, offset=None, tile=0, bf16x3=None):
+    """x_nhwc (N,H,W,Cin) contiguous fp32, w_krsc (Cout,3,3,Cin), offset (N,18,H,W) or None -> (N,H,W,Cout).
+    bf16x3: None = the JDET_CONV_BF16X3 route for big shapes, True / False = that route forced on / off (it never
+    applies to a forced tile or the deformable form)"""
     L.need_device(x_nhwc, w_krsc, bias, rowmask, offset)
     N, H, W, Cin = x_nhwc.shape
     Cout = w_krsc.shape[0]
@@ -38,6 +83,8 @@ def conv3x3_nhwc(x_nhwc, w_krsc, bias=None, relu=False, rowmask=None, offset=Non
         raise ValueError("weight %r does not match input channels %d" % (tuple(w_krsc.shape), Cin))
     if offset is not None and tuple(offset.shape) != (N, 18, H, W):
         raise ValueError("offset must be (N, 18, H, W), got %r" % (tuple(offset.shape),))
+    if (BF16X3 if bf16x3 is None else bf16x3) and tile == 0 and offset is None and bf16x3_big(N * H * W, Cin, Cout):
+        return conv3x3_bf16x3_nhwc(x_nhwc, w_krsc, bias, relu, rowmask)
     x_nhwc, w_krsc = L.f32c(x_nhwc), L.f32c(w_krsc)
     y = torch.empty((N, H, W, Cout), dtype=torch.float32, device=x_nhwc.device)
     ws, nbytes = None, 0
@@ -492,7 +539,8 @@ def _is_1x1(x, weight, stride, padding, groups):
 class _ConvBiasAct(torch.autograd.Function):
     """y = [relu](conv(x, w) + b).  Forward: the implicit-GEMM kernel (`igemm`: 3x3 / stride 1 / pad 1 only) or the
     library convolution; backward: bias gradient and ReLU mask in one pass (`bias_act_backward`), then the library's
-    data / weight gradients (with DGRAD, for the igemm shapes: grad_x by the igemm kernel on the flipped weights).
+    data / weight gradients (with DGRAD, for the igemm shapes: grad_x by the igemm kernel on the flipped weights; with
+    BF16X3_DGRAD, for the big shapes: grad_x by the bf16 three-way-split kernel on the flipped weights).
     `row_sparse` (igemm layers): both gradients from the non-zero rows of the incoming gradient (`_rows_backward`)."""
 
     @staticmethod
@@ -562,8 +610,14 @@ class _ConvBiasAct(torch.autograd.Function):
                 and (g.shape[0] * g.shape[2] * g.shape[3] + 16) * max(weight.shape[0], weight.shape[1]) < 2 ** 30):
             gx, gw = _rows_backward(g, x, weight, need[0], need[1])
             return gx, gw, gb, None, None, None, None, None, None, None, None
-        if need[0] and igemm and DGRAD and supported(weight.shape[0], weight.shape[1]):
-            gx = conv3x3_nhwc(L.f32c(g.permute(0, 2, 3, 1)), dgrad_weight(weight)).permute(0, 3, 1, 2)
+        if (need[0] and igemm and BF16X3_DGRAD and g.is_cuda and g.dtype == torch.float32
+                and bf16x3_big(g.shape[0] * g.shape[2] * g.shape[3], weight.shape[0], weight.shape[1])):
+            # the big layers: grad_x by the split kernel on the flipped weights (the bank refreshed once per backward
+            # pass, as for the rows route: the fused optimizer step does not move the version counters)
+            gx = conv3x3_nhwc(L.f32c(g.permute(0, 2, 3, 1)), _rows_dgrad_weight(weight), bf16x3=True).permute(0, 3, 1, 2)
+            need[0] = False
+        elif need[0] and igemm and DGRAD and supported(weight.shape[0], weight.shape[1]):
+            gx = conv3x3_nhwc(L.f32c(g.permute(0, 2, 3, 1)), dgrad_weight(weight), bf16x3=False).permute(0, 3, 1, 2)
             need[0] = False
         own_gw = need[1] and igemm and WGRAD and wgrad_supported(weight.shape[1], weight.shape[0])
         if own_gw:
