@@ -6,7 +6,7 @@ decode, the min-size predicate and the keywords of `proposal_table`."""
 import torch
 
 from jdet_amd.models.utils.level_pack import run_levels
-from jdet_amd.ops.conv_igemm import conv3x3_module, conv_module
+from jdet_amd.ops.conv_igemm import conv_module
 
 INVALID_SCORE = -1.0   # score of a padding row in a proposal table
 
@@ -15,7 +15,7 @@ def forward_single(head, x, mask=None):
     """`rpn_conv` (3x3, relu) -> (`rpn_cls`, `rpn_reg`); bound as a method by the three-conv heads.  `mask` is part of
     `run_levels`' callback signature (the gap mask of a packed input): the 1x1 layers read no neighbours, so a packed
     input needs none here"""
-    x = conv3x3_module(head.rpn_conv, x, relu=True)
+    x = conv_module(head.rpn_conv, x, relu=True)
     return conv_module(head.rpn_cls, x), conv_module(head.rpn_reg, x)
 
 

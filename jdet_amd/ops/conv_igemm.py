@@ -33,6 +33,25 @@ def weight_krsc(weight):
     return L.f32c(weight.permute(0, 2, 3, 1))
 
 
+def _plain_conv(conv):
+    """a plain nn.Conv2d (zeros padding, given as numbers) called outside autocast"""
+    return (type(conv).__name__ == "Conv2d" and conv.padding_mode == "zeros" and not isinstance(conv.padding, str)
+            and not torch.is_autocast_enabled())
+
+
+def _fits_32bit(positions, cin, cout, pad=0):
+    """the kernels address with 32-bit byte offsets (`pad`: rows a kernel may address past the map)"""
+    return (positions + pad) * max(cin, cout) < 2 ** 30
+
+
+def _check_shapes(N, H, W, Cin, w_krsc=None, offset=None):
+    """the weight (Cout,3,3,Cin) matches x (N,H,W,Cin); the offset is (N,18,H,W)"""
+    if w_krsc is not None and w_krsc.shape[1:] != (3, 3, Cin):
+        raise ValueError("weight %r does not match input channels %d" % (tuple(w_krsc.shape), Cin))
+    if offset is not None and tuple(offset.shape) != (N, 18, H, W):
+        raise ValueError("offset must be (N, 18, H, W), got %r" % (tuple(offset.shape),))
+
+
 # The big dense layers on the bf16 matrix pipe through an exact three-way split of the fp32 operands (csrc/conv_bf16x3.hip,
 # profiles/conv_bf16x3.md): the shapes the fp32 kernel gives its 128 x 128 tile (at least 512 of them) with Cin % 32 == 0,
 # automatic tile, plain form -- with and without gradients alike (one kernel per shape: the no-grad route of a layer
@@ -50,7 +69,7 @@ def bf16x3_supported(cin, cout):
 def bf16x3_big(positions, cin, cout):
     """the shapes the split kernel is routed to: conv_igemm.hip's `big` rule (128 x 128 tiles >= 512), channels it takes"""
     # (plain integer tests first: every fused 3x3 call of every model passes here, most of them below the rule)
-    if ((positions + 127) // 128) * ((cout + 127) // 128) < 512 or cin % 32 != 0 or positions * max(cin, cout) >= 2 ** 30:
+    if ((positions + 127) // 128) * ((cout + 127) // 128) < 512 or cin % 32 != 0 or not _fits_32bit(positions, cin, cout):
         return False
     return bf16x3_supported(cin, cout)
 
@@ -61,8 +80,7 @@ def conv3x3_bf16x3_nhwc(x_nhwc, w_krsc, bias=None, relu=False, rowmask=None):
     L.need_device(x_nhwc, w_krsc, bias, rowmask)
     N, H, W, Cin = x_nhwc.shape
     Cout = w_krsc.shape[0]
-    if w_krsc.shape[1:] != (3, 3, Cin):
-        raise ValueError("weight %r does not match input channels %d" % (tuple(w_krsc.shape), Cin))
+    _check_shapes(N, H, W, Cin, w_krsc)
     x_nhwc, w_krsc = L.f32c(x_nhwc), L.f32c(w_krsc)
     y = torch.empty((N, H, W, Cout), dtype=torch.float32, device=x_nhwc.device)
     L.check(L.lib().jdet_conv3x3_bf16x3_forward(
@@ -79,10 +97,7 @@ def conv3x3_nhwc(x_nhwc, w_krsc, bias=None, relu=False, rowmask=None, offset=Non
     L.need_device(x_nhwc, w_krsc, bias, rowmask, offset)
     N, H, W, Cin = x_nhwc.shape
     Cout = w_krsc.shape[0]
-    if w_krsc.shape[1:] != (3, 3, Cin):
-        raise ValueError("weight %r does not match input channels %d" % (tuple(w_krsc.shape), Cin))
-    if offset is not None and tuple(offset.shape) != (N, 18, H, W):
-        raise ValueError("offset must be (N, 18, H, W), got %r" % (tuple(offset.shape),))
+    _check_shapes(N, H, W, Cin, w_krsc, offset)
     if (BF16X3 if bf16x3 is None else bf16x3) and tile == 0 and offset is None and bf16x3_big(N * H * W, Cin, Cout):
         return conv3x3_bf16x3_nhwc(x_nhwc, w_krsc, bias, relu, rowmask)
     x_nhwc, w_krsc = L.f32c(x_nhwc), L.f32c(w_krsc)
@@ -112,9 +127,10 @@ def conv3x3(x, weight, bias=None, relu=False, offset=None, tile=0):
 MIN_POSITIONS = int(os.environ.get("JDET_CONV_MIN_POS", "1"))
 DEFORM_MIN_POSITIONS = 32768
 ENABLED = os.environ.get("JDET_CONV_IGEMM", "1") == "1"     # A/B switch for measurements
-# Train step: the fused forward + the library's data / weight gradients (`_Conv3x3BiasAct`).  S2ANet step 30.05 ms with
-# it, 30.37 ms without (two A/B pairs, profiles/r03_conv_igemm.md); JDET_CONV_IGEMM_TRAIN=0 switches it off.
+# Train step: the fused forward with a backward of its own (`_ConvBiasAct`).  S2ANet step 30.05 ms with it, 30.37 ms
+# without (two A/B pairs, profiles/r03_conv_igemm.md); JDET_CONV_IGEMM_TRAIN=0 switches it off.
 TRAIN = os.environ.get("JDET_CONV_IGEMM_TRAIN", "1") == "1"
+
 
 def needs_grad(*tensors):
     return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
@@ -127,7 +143,7 @@ def preferred(x, weight, min_positions=None):
     N, Cin, H, W = x.shape
     if tuple(weight.shape[1:]) != (Cin, 3, 3) or not supported(Cin, weight.shape[0]):
         return False
-    if N * H * W * max(Cin, weight.shape[0]) >= 2 ** 30:          # the kernel addresses with 32-bit byte offsets
+    if not _fits_32bit(N * H * W, Cin, weight.shape[0]):
         return False
     return N * H * W >= (MIN_POSITIONS if min_positions is None else min_positions)
 
@@ -146,8 +162,7 @@ def conv3x3_wgrad_nhwc(x_nhwc, gy_nhwc, offset=None, out=None, ksplit=0, rows=No
     Cout = gy_nhwc.shape[3]
     if tuple(gy_nhwc.shape[:3]) != (N, H, W):
         raise ValueError("gy %r does not match x %r" % (tuple(gy_nhwc.shape), tuple(x_nhwc.shape)))
-    if offset is not None and tuple(offset.shape) != (N, 18, H, W):
-        raise ValueError("offset must be (N, 18, H, W), got %r" % (tuple(offset.shape),))
+    _check_shapes(N, H, W, Cin, None, offset)
     x_nhwc, gy_nhwc = L.f32c(x_nhwc), L.f32c(gy_nhwc)
     if out is None:
         out = torch.zeros((Cout, 3, 3, Cin), dtype=torch.float32, device=x_nhwc.device)
@@ -164,19 +179,15 @@ def conv3x3_wgrad(x, gy, offset=None, ksplit=0):
     return gw.permute(0, 3, 1, 2)
 
 
-# Weight gradient of the igemm layers by csrc/conv_wgrad.hip (default since round 6; JDET_CONV_WGRAD=0: the library's).  Several uses
-# of ONE weight inside one backward pass (a tower shared by the pyramid levels) accumulate into the buffer the first use
-# returned: the kernel adds in place, so the engine neither zero-fills per call nor sums the uses afterwards.
-# Measured (profiles/r04_conv_wgrad.md): the kernel runs 91 % MFMA-busy in cycles and ties the library's in isolation
-# (312 vs 314-326 us at 2 x 128^2 x 256), but inside the autotuned S2ANet step the library's pick is faster than its
-# stand-alone time: 29.28 ms with this switch on against 29.02-29.06 ms off -- so it is off by default.  (Round 5: the same
-# layers through the backbone's 64 x 64-tile entry point tie the library as well: 27.885 vs 27.904 ms, profiles/r05_conv_bn.md.)
-# Round 6: ON by default.  With 128 x 64 tiles for the tower shape (310 us against 360 on 128 x 128 and the library's 326 incl.
-# its zero fill), raw buffer atomics with SGPR row offsets in the epilogue and 32-bit prologue arithmetic the own kernel first
-# tied the library in the step (26.48 vs 26.48-26.52 ms) and then beat it: 26.075 vs 26.173 ms (three same-box pairs, all three in
-# its favour), 744 -> 727 launches (18 library zero fills and 8 accumulation adds fewer): profiles/r06_conv_prefetch.md.
-# JDET_CONV_WGRAD=0: the library's.
+# Weight gradient of the igemm layers by csrc/conv_wgrad.hip, on by default; JDET_CONV_WGRAD=0 selects the library's, which
+# the shapes `wgrad_supported` refuses take in any case.  Several uses of ONE weight inside one backward pass (a tower
+# shared by the pyramid levels) accumulate into the buffer the first use returned: the kernel adds in place, so the engine
+# neither zero-fills per call nor sums the uses afterwards.  In the S2ANet step the own kernel measures 26.075 against the
+# library's 26.173 ms with 744 -> 727 launches (18 library zero fills and 8 accumulation adds fewer:
+# profiles/r06_conv_prefetch.md); the kernel in isolation is in profiles/r04_conv_wgrad.md.
 WGRAD = os.environ.get("JDET_CONV_WGRAD", "1") == "1"
+
+
 def _wgrad_call(x_nhwc, gy_nhwc, offset, N, H, W, Cin, Cout, out_ptr, ksplit, rows=None):
     if rows is not None:
         if offset is not None:
@@ -187,7 +198,7 @@ def _wgrad_call(x_nhwc, gy_nhwc, offset, N, H, W, Cin, Cout, out_ptr, ksplit, ro
                                       N, H, W, Cin, Cout, out_ptr, int(ksplit), L.stream_ptr(x_nhwc))
 
 
-_GW_ACC = {}           # weight.data_ptr() -> (backward pass id, device pointer of the (Cout,3,3,Cin) buffer, its shape)
+_GW_ACC = {}           # weight.data_ptr() -> (backward pass id, device pointer of the (Cout,3,3,Cin) buffer, its shape, stream)
 
 
 def shared_wgrad(weight, x_nhwc, gy_nhwc, offset=None, rows=None):
@@ -204,7 +215,7 @@ def shared_wgrad(weight, x_nhwc, gy_nhwc, offset=None, rows=None):
     # buffer whose hand-over to AccumulateGrad the engine orders only against the first use's stream -- it gets its own
     # gradient tensor and autograd adds the two (advisor finding, round 4)
     stream = torch.cuda.current_stream(x_nhwc.device).cuda_stream if x_nhwc.is_cuda else 0
-    if hit is not None and len(hit) > 3 and hit[3] != stream:
+    if hit is not None and hit[3] != stream:
         hit = None
     if tid >= 0 and hit is not None and hit[0] == tid and hit[2] == (Cout, Cin, x_nhwc.device):
         N, H, W, _ = x_nhwc.shape
@@ -215,12 +226,6 @@ def shared_wgrad(weight, x_nhwc, gy_nhwc, offset=None, rows=None):
     if tid >= 0 and (_GW_ACC.get(key) is None or _GW_ACC[key][0] != tid):
         _GW_ACC[key] = (tid, buf.data_ptr(), (Cout, Cin, x_nhwc.device), stream)
     return buf.permute(0, 3, 1, 2)
-
-
-_FLIPPED = {}          # id(weight) -> (data_ptr, version, tensor): the data-gradient weights of the current step
-# grad_x through this kernel (flipped weights): 296 vs 341 us against the library's data gradient in isolation
-# (scripts/wgrad_bar.py), but no difference inside the autotuned train step (30.30 vs 30.30 ms): off by default.
-DGRAD = os.environ.get("JDET_CONV_IGEMM_DGRAD", "0") == "1"
 
 
 class _WeightRef:
@@ -239,38 +244,53 @@ _DGRAD_BANKS = {}      # device -> {"items": {id(weight): _WeightRef}, "bank": D
 
 def dgrad_weight(weight):
     """(Cout, Cin, 3, 3) -> (Cin, 3, 3, Cout) contiguous with the taps flipped: grad_x = conv3x3(grad_y, this).  The
-    weights seen so far on a device live in ONE bank (conv_bn.DgradBank: one launch rewrites all of them when a version
-    moved, i.e. once per training step -- the per-weight flip + copy pair was 2 launches x 19 weights per S2ANet step);
-    weights that are not channels-last fp32 device tensors take the per-weight form."""
-    st = None
-    if weight.is_cuda and weight.dtype == torch.float32 and weight.permute(0, 2, 3, 1).is_contiguous() \
-            and not torch.cuda.is_current_stream_capturing():
-        from jdet_amd.ops.conv_bn import DgradBank
-        st = _DGRAD_BANKS.setdefault(weight.device, {"items": {}, "bank": None})
-        it = st["items"].get(id(weight))
-        if it is None or it.weight is not weight or any(v.weight is None for v in st["items"].values()):
-            live = {k: v for k, v in st["items"].items() if v.weight is not None}
-            it = live[id(weight)] = _WeightRef(weight)
-            st["items"] = live
-            st["bank"] = DgradBank(list(live.values()))
-        return st["bank"].get(it)
-    if weight.is_cuda and torch.cuda.is_current_stream_capturing():
-        st = _DGRAD_BANKS.get(weight.device)
-        it = st["items"].get(id(weight)) if st else None
-        if it is not None and it.weight is weight and st["bank"].buf is not None:
-            return st["bank"].get(it)          # (built by the eager warm-up steps: a refresh is one kernel, capturable)
-    key, stamp = id(weight), (weight.data_ptr(), weight._version)
-    hit = _FLIPPED.get(key)
-    if hit is None or hit[0] != stamp:
-        hit = (stamp, weight.detach().flip(2, 3).permute(1, 2, 3, 0).contiguous())
-        _FLIPPED[key] = hit
-    return hit[1]
+    channels-last fp32 weights seen so far on a device live in ONE bank (conv_bn.DgradBank: one launch rewrites all of
+    them -- the per-weight flip + copy pair was 2 launches x 19 weights per S2ANet step), refreshed ONCE PER BACKWARD
+    PASS whatever the version counters say -- the fused multi-tensor SGD step (optims/optimizer.py) updates parameters
+    without moving `_version` -- and on every call outside a backward pass.  Under graph capture the flip is part of the
+    captured pass and its result lives in the graph's pool: nothing a replay reads can be freed or go stale outside it.
+    Weights of another layout or dtype, or off the device, take the per-weight form, recomputed on every call."""
+    if (not weight.is_cuda or weight.dtype != torch.float32 or not weight.permute(0, 2, 3, 1).is_contiguous()
+            or torch.cuda.is_current_stream_capturing()):
+        return weight.detach().flip(2, 3).permute(1, 2, 3, 0).contiguous()
+    from jdet_amd.ops.conv_bn import DgradBank
+    st = _DGRAD_BANKS.setdefault(weight.device, {"items": {}, "bank": None})
+    it = st["items"].get(id(weight))
+    if it is None or it.weight is not weight or any(v.weight is None for v in st["items"].values()):
+        live = {k: v for k, v in st["items"].items() if v.weight is not None}
+        it = live[id(weight)] = _WeightRef(weight)
+        st["items"] = live
+        st["bank"] = DgradBank(list(live.values()))
+    # `get` builds the bank's buffer and refreshes it if a version or pointer moved; where it did, the first call of a
+    # pass rewrites the bank a second time (one launch, on the passes after a bank was built or a version moved)
+    wd = st["bank"].get(it)
+    tid = torch._C._current_graph_task_id()
+    if tid < 0 or st.get("pass") != tid:
+        st["bank"].refresh()
+        st["pass"] = tid
+    return wd
 
 
 # bias [+ ReLU] backward as ONE pass (csrc/frozen_bn.hip: jdet_bias_act_backward) instead of the framework's
 # threshold_backward + per-channel reduce pair; JDET_BIAS_ACT_BWD=0 switches back (A/B: profiles/r03_conv_igemm.md).
 BIAS_ACT_BWD = os.environ.get("JDET_BIAS_ACT_BWD", "1") == "1"
 _BWD_WS = {}
+
+
+def _scratch(cache, nbytes, device):
+    """at least `nbytes` (and at least 1) bytes of scratch for the current stream of `device`: in eager mode from `cache`,
+    one buffer of at least 1 MiB per (device, stream) that the next call on the stream reuses"""
+    if torch.cuda.is_current_stream_capturing():
+        # the address is baked into the graph: scratch from the capturing graph's own pool, never from (or into) the
+        # cache -- an evicted cache entry would leave replays writing partial sums to freed memory
+        return torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=device)
+    key = (device.index, torch.cuda.current_stream(device).cuda_stream)
+    ws = cache.get(key)
+    if ws is None or ws.numel() < nbytes:
+        while len(cache) >= 8:       # streams come and go: keep the scratch cache bounded (oldest entry out)
+            cache.pop(next(iter(cache)))
+        ws = cache[key] = torch.empty((max(nbytes, 1 << 20),), dtype=torch.uint8, device=device)
+    return ws
 
 
 def _bias_bwd_supported(c):
@@ -300,17 +320,7 @@ def bias_act_backward(g, y, relu):
     gn = L.f32c(g.permute(0, 2, 3, 1))
     P = N * H * W
     nbytes = L.lib().jdet_frozen_bn_act_backward_workspace(P, C)
-    if torch.cuda.is_current_stream_capturing():
-        # the address is baked into the graph: scratch from the capturing graph's own pool, never from (or into) the
-        # cache -- an evicted cache entry would leave replays writing partial sums to freed memory
-        ws = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=g.device)
-    else:
-        key = (g.device.index, torch.cuda.current_stream(g.device).cuda_stream)
-        ws = _BWD_WS.get(key)
-        if ws is None or ws.numel() < nbytes:
-            while len(_BWD_WS) >= 8:       # streams come and go: keep the scratch cache bounded (oldest entry out)
-                _BWD_WS.pop(next(iter(_BWD_WS)))
-            ws = _BWD_WS[key] = torch.empty((max(nbytes, 1 << 20),), dtype=torch.uint8, device=g.device)
+    ws = _scratch(_BWD_WS, nbytes, g.device)
     gb = torch.empty((C,), dtype=torch.float32, device=g.device)
     gp = torch.empty_like(gn) if relu else gn
     yn = L.f32c(y.permute(0, 2, 3, 1)) if relu else None
@@ -325,7 +335,7 @@ def bias_act_backward(g, y, relu):
 # is a routing hint only: any gradient is computed correctly, a dense one just slower.  JDET_CONV_ROWS=0: the dense
 # kernels (A/B).
 ROWS = os.environ.get("JDET_CONV_ROWS", "1") == "1"
-_ROWS_WS = {}
+_ROWS_WS = {}          # (a cache of its own: the lists `rows_nonzero` returns outlive the next node's bias pass)
 
 
 def wgrad_rows_workers(cin, cout):
@@ -335,19 +345,6 @@ def wgrad_rows_workers(cin, cout):
 
 def rows_supported(cin, cout):
     return bool(L.lib().jdet_conv3x3_rows_supported(int(cin), int(cout)))
-
-
-def _rows_scratch(nbytes, device):
-    """bias_act_backward's rule: cached per (device, stream) in eager mode, from the capturing graph's pool under capture"""
-    if torch.cuda.is_current_stream_capturing():
-        return torch.empty((nbytes,), dtype=torch.uint8, device=device)
-    key = (device.index, torch.cuda.current_stream(device).cuda_stream)
-    ws = _ROWS_WS.get(key)
-    if ws is None or ws.numel() < nbytes:
-        while len(_ROWS_WS) >= 8:
-            _ROWS_WS.pop(next(iter(_ROWS_WS)))
-        ws = _ROWS_WS[key] = torch.empty((max(nbytes, 1 << 20),), dtype=torch.uint8, device=device)
-    return ws
 
 
 def rows_nonzero(g_nhwc, scratch=None):
@@ -361,7 +358,7 @@ def rows_nonzero(g_nhwc, scratch=None):
     g_nhwc = L.f32c(g_nhwc)
     wsb = L.lib().jdet_rows_nonzero_workspace(N, H, W)
     total = 8 * P + 16 + wsb + P            # rows | rows_dilated | counts (padded to 16) | workspace (16 n) | flags
-    buf = _rows_scratch(total, g_nhwc.device) if scratch is None else scratch
+    buf = _scratch(_ROWS_WS, total, g_nhwc.device) if scratch is None else scratch
     rows = buf[:4 * P].view(torch.int32)
     drows = buf[4 * P:8 * P].view(torch.int32)
     counts = buf[8 * P:8 * P + 8].view(torch.int32)
@@ -390,28 +387,6 @@ def conv3x3_dgrad_rows_nhwc(gy_nhwc, wd_crsk, rows, count_ptr, out=None):
     return out
 
 
-def _rows_dgrad_weight(weight):
-    """the (Cin, 3, 3, Cout) flipped weights for the rows data gradient.  Eager: `dgrad_weight`'s bank (one launch rewrites
-    every weight in it), refreshed ONCE PER BACKWARD PASS whatever the version counters say -- the fused multi-tensor SGD
-    step (optims/optimizer.py) updates parameters without moving `_version`.  Under graph capture the flip is part of the
-    captured pass and its result lives in the graph's pool: nothing a replay reads can be freed or go stale outside it."""
-    if torch.cuda.is_current_stream_capturing() or not weight.is_cuda:
-        return weight.detach().flip(2, 3).permute(1, 2, 3, 0).contiguous()
-    wd = dgrad_weight(weight)                       # (builds / extends the bank; refreshes it if a version moved)
-    st = _DGRAD_BANKS.get(weight.device)
-    if st is None or st["bank"] is None or id(weight) not in st["items"]:
-        return dgrad_weight_fresh(weight)           # not a bank weight (layout, dtype): the per-weight form, recomputed
-    tid = torch._C._current_graph_task_id()
-    if tid < 0 or st.get("pass") != tid:
-        st["bank"].refresh()
-        st["pass"] = tid
-    return wd
-
-
-def dgrad_weight_fresh(weight):
-    return weight.detach().flip(2, 3).permute(1, 2, 3, 0).contiguous()
-
-
 def _rows_backward(g, x, weight, need_x, need_w):
     """(grad_x, grad_w) of a plain 3x3 / stride 1 / pad 1 convolution from the non-zero rows of g (N, Cout, H, W)"""
     gn, xn = L.f32c(g.permute(0, 2, 3, 1)), L.f32c(x.permute(0, 2, 3, 1))
@@ -420,7 +395,7 @@ def _rows_backward(g, x, weight, need_x, need_w):
     if need_w:
         gw = shared_wgrad(weight, xn, gn, rows=(rows, counts.data_ptr()))
     if need_x:
-        gx = conv3x3_dgrad_rows_nhwc(gn, _rows_dgrad_weight(weight), drows, counts.data_ptr() + 4).permute(0, 3, 1, 2)
+        gx = conv3x3_dgrad_rows_nhwc(gn, dgrad_weight(weight), drows, counts.data_ptr() + 4).permute(0, 3, 1, 2)
     return gx, gw
 
 
@@ -461,8 +436,7 @@ def conv3x3_rows_forward_nhwc(x_nhwc, w_krsc, bias, relu, rowmask, rows, count_p
     L.need_device(x_nhwc, w_krsc, bias, rowmask, rows, out)
     N, H, W, Cin = x_nhwc.shape
     Cout = w_krsc.shape[0]
-    if tuple(w_krsc.shape[1:]) != (3, 3, Cin):
-        raise ValueError("weight %r does not match input channels %d" % (tuple(w_krsc.shape), Cin))
+    _check_shapes(N, H, W, Cin, w_krsc)
     x_nhwc, w_krsc = L.f32c(x_nhwc), L.f32c(w_krsc)
     zero = out is None
     if zero:
@@ -475,23 +449,21 @@ def conv3x3_rows_forward_nhwc(x_nhwc, w_krsc, bias, relu, rowmask, rows, count_p
 
 
 class _ConvBiasActRows(torch.autograd.Function):
-    """y = [relu](conv3x3(x, w) + b) [* rowmask] on the listed rows, 0 on every other row.  It saves what `_ConvBiasAct`
-    saves and its backward IS that one's rows branch: exact wherever the incoming gradient is zero outside the rows
+    """y = [relu](conv3x3(x, w) + b) [* rowmask] on the listed rows, 0 on every other row.  Its backward is
+    `_conv_backward` with `row_sparse` set: exact wherever the incoming gradient is zero outside the rows
     whose 3x3 neighbourhoods the list covers (a row that holds 0 has the ReLU mask [y > 0] = 0, as a masked row has)."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, relu, rowmask, rows, count_ptr):
         y = conv3x3_rows_forward_nhwc(L.f32c(x.permute(0, 2, 3, 1)), weight_krsc(weight), bias, relu, rowmask, rows,
                                       count_ptr).permute(0, 3, 1, 2)
-        ctx.k1 = False
-        ctx.row_sparse = True
-        ctx.cfg = (bool(relu), [1, 1], [1, 1], [1, 1], 1, True, bias is not None)
+        ctx.cfg = (bool(relu), bias is not None, [1, 1], [1, 1], [1, 1], 1, True, False, True)
         ctx.save_for_backward(x, weight, y if relu else None)
         return y
 
     @staticmethod
     def backward(ctx, g):
-        return _ConvBiasAct.backward(ctx, g)[:7]
+        return _conv_backward(ctx.saved_tensors, ctx.cfg, ctx.needs_input_grad, g) + (None,) * 4
 
 
 def rows_tower_applicable(convs, x, positions=None):
@@ -500,17 +472,16 @@ def rows_tower_applicable(convs, x, positions=None):
     gathered tile takes, both switches on."""
     if not (ROWS and ROWS_FWD and TRAIN and BIAS_ACT_BWD and 1 <= len(convs) <= 2):
         return False
-    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4) or torch.is_autocast_enabled():
+    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4):
         return False
     for conv in convs:
-        if not (type(conv).__name__ == "Conv2d" and conv.padding_mode == "zeros" and not isinstance(conv.padding, str)
-                and _is_igemm_conv(conv) and conv.weight.dtype == torch.float32 and conv.bias is not None
-                and conv.bias.requires_grad and _bias_bwd_supported(conv.out_channels)
+        if not (_plain_conv(conv) and _is_igemm_conv(conv) and conv.weight.dtype == torch.float32
+                and conv.bias is not None and conv.bias.requires_grad and _bias_bwd_supported(conv.out_channels)
                 and rows_forward_supported(conv.in_channels, conv.out_channels)
                 and rows_supported(conv.in_channels, conv.out_channels)):
             return False
     P = x.shape[0] * x.shape[2] * x.shape[3] if positions is None else positions
-    return (P + 16) * max([c.in_channels for c in convs] + [c.out_channels for c in convs]) < 2 ** 30
+    return _fits_32bit(P, max(c.in_channels for c in convs), max(c.out_channels for c in convs), 16)
 
 
 def rows_tower(convs, x, flags, rowmask=None):
@@ -536,11 +507,80 @@ def _is_1x1(x, weight, stride, padding, groups):
             and x.is_contiguous(memory_format=torch.channels_last))
 
 
+def _conv1x1_backward(g, x, weight, stride, padding, dilation, groups, need):
+    """(grad_x, grad_w) of a stride-1 1x1 convolution of a channels-last map (`_is_1x1`)"""
+    # the data gradient of a 1x1 convolution as gy . W (18 % faster than the library's over the ResNet / FPN
+    # shapes), the weight gradient as gy^T . x only on small maps (its reduction runs over the positions)
+    N, Ci, H, W = x.shape
+    Co = weight.shape[0]
+    g = g.contiguous(memory_format=torch.channels_last)
+    gm = g.permute(0, 2, 3, 1).reshape(-1, Co)
+    gx = gw1 = None
+    if need[0]:
+        gx = (gm @ weight.view(Co, Ci)).view(N, H, W, Ci).permute(0, 3, 1, 2)
+        need[0] = False
+    if need[1] and N * H * W <= 4096:
+        gw1 = (gm.t() @ x.permute(0, 2, 3, 1).reshape(-1, Ci)).view(Co, Ci, 1, 1)
+        need[1] = False
+    _, gw, _ = torch.ops.aten.convolution_backward(g, x, weight, None, stride, padding, dilation, False,
+                                                   [0, 0], groups, need) if any(need) else (None, None, None)
+    gw = gw1 if gw1 is not None else gw
+    if gw is not None and gw.stride() != weight.stride() and gw.numel() == weight.numel():
+        # (Cout, Cin, 1, 1) is one memory order under two stride spellings: the parameter's own keeps the
+        # gradient layout contract (DDP's bucket views otherwise copy and warn)
+        gw = gw.as_strided(weight.shape, weight.stride())
+    return gx, gw
+
+
+def _dgrad_route(g, weight, row_sparse, need_x, need_w):
+    """who computes the data gradient of an igemm layer: "rows" = `_rows_backward` (the weight gradient with it),
+    "bf16x3" = the split kernel on the flipped weights (the big layers), None = the library"""
+    if not (g.is_cuda and g.dtype == torch.float32):
+        return None
+    P, cout, cin = g.shape[0] * g.shape[2] * g.shape[3], weight.shape[0], weight.shape[1]
+    if row_sparse and ROWS and (need_x or need_w) and rows_supported(cin, cout) and _fits_32bit(P, cout, cin, 16):
+        return "rows"
+    if need_x and BF16X3_DGRAD and bf16x3_big(P, cout, cin):
+        return "bf16x3"
+    return None
+
+
+def _conv_backward(saved, cfg, needs, g):
+    """(grad_x, grad_w, grad_b) of y = [relu](conv(x, w) + b).  saved: (x, w, y or None); cfg: (relu, has_bias, stride,
+    padding, dilation, groups, igemm, k1, row_sparse) as `_ConvBiasAct.forward` describes them; needs: which of the three
+    are wanted.  Bias gradient and ReLU mask in one pass (`bias_act_backward`), then the own kernels where they apply,
+    then the library's data / weight gradients for what is left."""
+    x, weight, y = saved
+    relu, has_bias, stride, padding, dilation, groups, igemm, k1, row_sparse = cfg
+    gb = None
+    if has_bias and needs[2]:
+        g, gb = bias_act_backward(g, y, relu)
+    elif relu:
+        g = torch.ops.aten.threshold_backward(g, y, 0)
+    need = [needs[0], needs[1], False]
+    if k1:
+        return _conv1x1_backward(g, x, weight, stride, padding, dilation, groups, need) + (gb,)
+    route = _dgrad_route(g, weight, row_sparse, need[0], need[1]) if igemm else None
+    if route == "rows":
+        return _rows_backward(g, x, weight, need[0], need[1]) + (gb,)
+    gx = gw = None
+    if route == "bf16x3":
+        gx = conv3x3_nhwc(L.f32c(g.permute(0, 2, 3, 1)), dgrad_weight(weight), bf16x3=True).permute(0, 3, 1, 2)
+        need[0] = False
+    if need[1] and igemm and WGRAD and wgrad_supported(weight.shape[1], weight.shape[0]):
+        gw = shared_wgrad(weight, x.permute(0, 2, 3, 1), g.permute(0, 2, 3, 1))      # (None: added to an earlier use's)
+        need[1] = False
+    if any(need):
+        lx, lw, _ = torch.ops.aten.convolution_backward(g, x, weight, None, stride, padding, dilation, False, [0, 0],
+                                                        groups, need)
+        gx, gw = (lx if need[0] else gx), (lw if need[1] else gw)
+    return gx, gw, gb
+
+
 class _ConvBiasAct(torch.autograd.Function):
     """y = [relu](conv(x, w) + b).  Forward: the implicit-GEMM kernel (`igemm`: 3x3 / stride 1 / pad 1 only) or the
-    library convolution; backward: bias gradient and ReLU mask in one pass (`bias_act_backward`), then the library's
-    data / weight gradients (with DGRAD, for the igemm shapes: grad_x by the igemm kernel on the flipped weights; with
-    BF16X3_DGRAD, for the big shapes: grad_x by the bf16 three-way-split kernel on the flipped weights).
+    library convolution; backward: `_conv_backward` (with BF16X3_DGRAD, for the big igemm shapes: grad_x by the bf16
+    three-way-split kernel on the flipped weights).
     `row_sparse` (igemm layers): both gradients from the non-zero rows of the incoming gradient (`_rows_backward`)."""
 
     @staticmethod
@@ -566,69 +606,14 @@ class _ConvBiasAct(torch.autograd.Function):
             y = torch.ops.aten.convolution(x, weight, bias, stride, padding, dilation, False, [0, 0], groups)
             if relu:
                 y = torch.relu_(y)
-        ctx.k1 = k1
-        ctx.row_sparse = bool(row_sparse) and bool(igemm)
-        ctx.cfg = (bool(relu), list(stride), list(padding), list(dilation), groups, bool(igemm), bias is not None)
+        ctx.cfg = (bool(relu), bias is not None, list(stride), list(padding), list(dilation), groups, bool(igemm), k1,
+                   bool(row_sparse))
         ctx.save_for_backward(x, weight, y if relu else None)
         return y
 
     @staticmethod
     def backward(ctx, g):
-        x, weight, y = ctx.saved_tensors
-        relu, stride, padding, dilation, groups, igemm, has_bias = ctx.cfg
-        gb = None
-        if has_bias and ctx.needs_input_grad[2]:
-            g, gb = bias_act_backward(g, y, relu)
-        elif relu:
-            g = torch.ops.aten.threshold_backward(g, y, 0)
-        need = [ctx.needs_input_grad[0], ctx.needs_input_grad[1], False]
-        gx = None
-        if ctx.k1:
-            # the data gradient of a 1x1 convolution as gy . W (18 % faster than the library's over the ResNet / FPN
-            # shapes), the weight gradient as gy^T . x only on small maps (its reduction runs over the positions)
-            N, Ci, H, W = x.shape
-            Co = weight.shape[0]
-            g = g.contiguous(memory_format=torch.channels_last)
-            gm = g.permute(0, 2, 3, 1).reshape(-1, Co)
-            gw1 = None
-            if need[0]:
-                gx = (gm @ weight.view(Co, Ci)).view(N, H, W, Ci).permute(0, 3, 1, 2)
-                need[0] = False
-            if need[1] and N * H * W <= 4096:
-                gw1 = (gm.t() @ x.permute(0, 2, 3, 1).reshape(-1, Ci)).view(Co, Ci, 1, 1)
-                need[1] = False
-            lx, gw, _ = torch.ops.aten.convolution_backward(g, x, weight, None, stride, padding, dilation, False,
-                                                            [0, 0], groups, need) if any(need) else (None, None, None)
-            gw = gw1 if gw1 is not None else gw
-            if gw is not None and gw.stride() != weight.stride() and gw.numel() == weight.numel():
-                # (Cout, Cin, 1, 1) is one memory order under two stride spellings: the parameter's own keeps the
-                # gradient layout contract (DDP's bucket views otherwise copy and warn)
-                gw = gw.as_strided(weight.shape, weight.stride())
-            return gx, gw, gb, None, None, None, None, None, None, None, None
-        if (ctx.row_sparse and ROWS and (need[0] or need[1]) and g.is_cuda and g.dtype == torch.float32
-                and rows_supported(weight.shape[1], weight.shape[0])
-                and (g.shape[0] * g.shape[2] * g.shape[3] + 16) * max(weight.shape[0], weight.shape[1]) < 2 ** 30):
-            gx, gw = _rows_backward(g, x, weight, need[0], need[1])
-            return gx, gw, gb, None, None, None, None, None, None, None, None
-        if (need[0] and igemm and BF16X3_DGRAD and g.is_cuda and g.dtype == torch.float32
-                and bf16x3_big(g.shape[0] * g.shape[2] * g.shape[3], weight.shape[0], weight.shape[1])):
-            # the big layers: grad_x by the split kernel on the flipped weights (the bank refreshed once per backward
-            # pass, as for the rows route: the fused optimizer step does not move the version counters)
-            gx = conv3x3_nhwc(L.f32c(g.permute(0, 2, 3, 1)), _rows_dgrad_weight(weight), bf16x3=True).permute(0, 3, 1, 2)
-            need[0] = False
-        elif need[0] and igemm and DGRAD and supported(weight.shape[0], weight.shape[1]):
-            gx = conv3x3_nhwc(L.f32c(g.permute(0, 2, 3, 1)), dgrad_weight(weight), bf16x3=False).permute(0, 3, 1, 2)
-            need[0] = False
-        own_gw = need[1] and igemm and WGRAD and wgrad_supported(weight.shape[1], weight.shape[0])
-        if own_gw:
-            gw = shared_wgrad(weight, x.permute(0, 2, 3, 1), g.permute(0, 2, 3, 1))
-            need[1] = False
-        lx, lw, _ = torch.ops.aten.convolution_backward(g, x, weight, None, stride, padding, dilation, False, [0, 0],
-                                                        groups, need) if any(need) else (None, None, None)
-        return (gx if gx is not None else lx), (gw if own_gw else lw), gb, None, None, None, None, None, None, None, None
-
-
-_Conv3x3BiasAct = _ConvBiasAct      # (name used by the round-3 notes)
+        return _conv_backward(ctx.saved_tensors, ctx.cfg, ctx.needs_input_grad, g) + (None,) * 8
 
 
 def conv3x3_bias_act(x, weight, bias=None, relu=False, rowmask=None, row_sparse=False):
@@ -650,8 +635,7 @@ def _is_igemm_conv(conv):
 def masked_conv_module(conv, x, rowmask, row_sparse=False):
     """`relu(conv(x)) * mask` in ONE kernel for a plain 3x3 / stride 1 / pad 1 nn.Conv2d with a bias where the fused
     kernel applies (the towers on a LevelPack); None = not applicable here, the caller multiplies."""
-    plain = (type(conv).__name__ == "Conv2d" and conv.padding_mode == "zeros" and not isinstance(conv.padding, str)
-             and not torch.is_autocast_enabled())
+    plain = _plain_conv(conv)
     grad = needs_grad(x, conv.weight, conv.bias)
     if not (plain and _is_igemm_conv(conv) and preferred(x, conv.weight) and (TRAIN or not grad)):
         return None
@@ -665,8 +649,7 @@ def conv_module(conv, x, relu=False, row_sparse=False):
     """`[relu](conv(x))` for a plain nn.Conv2d (zeros padding).  3x3 / stride 1 / pad 1 layers take the fused kernel
     when `preferred()` says so; any layer WITH a bias that needs gradients goes through `_ConvBiasAct`, whose backward
     produces the bias gradient and the ReLU mask in one pass; everything else is the library call it always was."""
-    plain = (type(conv).__name__ == "Conv2d" and conv.padding_mode == "zeros" and not isinstance(conv.padding, str)
-             and not torch.is_autocast_enabled())
+    plain = _plain_conv(conv)
     grad = needs_grad(x, conv.weight, conv.bias)
     # (prediction layers of 5 / 15 / 18 channels would run a 64-wide output tile three quarters empty: the library's
     # narrow-tile kernels keep their forward; their bias gradient still comes from the own column sum below)
@@ -679,6 +662,3 @@ def conv_module(conv, x, relu=False, row_sparse=False):
                                   conv.groups, False)
     y = conv(x)
     return torch.relu(y) if relu else y
-
-
-conv3x3_module = conv_module

@@ -172,6 +172,26 @@ def test_conv_module_route_matches_the_fp32_route():
             assert torch.equal(m(x), outs[0][0])          # the no-grad route is the same kernel
         assert len(calls) == 3
         assert (outs[0][0] == 0).float().mean().item() > 0.2     # the ReLU is active
+        # the weight updated behind its version counter (as the fused multi-tensor SGD step does): the flipped weights of
+        # the split data gradient follow (tests/test_gpu_conv_rows.py makes the same check for the rows route)
+        v = m.conv.weight._version
+        m.conv.weight.data.mul_(-1.5)
+        assert m.conv.weight._version == v
+        CI.BF16X3 = CI.BF16X3_DGRAD = False
+        with torch.no_grad():      # (the outputs near the ReLU threshold are other ones now)
+            g = g * (m(x).abs() > 1e-4)
+        outs = []
+        for on in (True, False):
+            CI.BF16X3 = CI.BF16X3_DGRAD = on
+            xi = x.clone().requires_grad_(True)
+            m.zero_grad()
+            m(xi).backward(g)
+            outs.append((xi.grad, m.conv.weight.grad.clone(), m.conv.bias.grad.clone()))
+        assert len(calls) == 5
+        for name, a, b in zip(("grad_x", "grad_w", "grad_b"), *outs):
+            err, bound = (a - b).abs().max().item(), 2e-4 * b.abs().max().item() + 1e-6
+            print("after the update, %s: max difference %.3e bound %.3e" % (name, err, bound))
+            assert err <= bound
     finally:
         CI.BF16X3, CI.BF16X3_DGRAD = saved
         CI.conv3x3_bf16x3_nhwc = real
