@@ -198,15 +198,17 @@ def _wgrad_call(x_nhwc, gy_nhwc, offset, N, H, W, Cin, Cout, out_ptr, ksplit, ro
                                       N, H, W, Cin, Cout, out_ptr, int(ksplit), L.stream_ptr(x_nhwc))
 
 
-_GW_ACC = {}           # weight.data_ptr() -> (backward pass id, device pointer of the (Cout,3,3,Cin) buffer, its shape, stream)
+# weight.data_ptr() -> (backward pass id, device pointer of the (Cout,3,3,Cin) buffer or None = no longer shared, its shape, stream)
+_GW_ACC = {}
 
 
 def shared_wgrad(weight, x_nhwc, gy_nhwc, offset=None, rows=None):
     """weight gradient of y = conv3x3(x, weight) [deformable with `offset`; `rows`: see conv3x3_wgrad_nhwc -- dense and
     row-list uses of one weight share the buffer like any others] for this use of `weight`, as autograd wants
     it: the first use in a backward pass returns a fresh (Cout, Cin, 3, 3) tensor (channels_last memory, so a
-    channels_last parameter takes it without a copy); later uses add into that tensor's memory and return None.  Only
-    the pointer is remembered -- a second reference would make AccumulateGrad clone the gradient instead of taking it."""
+    channels_last parameter takes it without a copy); later uses add into that tensor's memory and return None -- until
+    a use on another stream returns a tensor of its own: from then on every use of the pass does.  Only the pointer is
+    remembered -- a second reference would make AccumulateGrad clone the gradient instead of taking it."""
     tid = torch._C._current_graph_task_id()
     key = weight.data_ptr()          # (the saved tensor may come back in a new Python wrapper: the storage names the weight)
     Cout, Cin = weight.shape[0], weight.shape[1]
@@ -215,13 +217,17 @@ def shared_wgrad(weight, x_nhwc, gy_nhwc, offset=None, rows=None):
     # buffer whose hand-over to AccumulateGrad the engine orders only against the first use's stream -- it gets its own
     # gradient tensor and autograd adds the two (advisor finding, round 4)
     stream = torch.cuda.current_stream(x_nhwc.device).cuda_stream if x_nhwc.is_cuda else 0
-    if hit is not None and hit[3] != stream:
-        hit = None
     if tid >= 0 and hit is not None and hit[0] == tid and hit[2] == (Cout, Cin, x_nhwc.device):
-        N, H, W, _ = x_nhwc.shape
-        x_nhwc, gy_nhwc = L.f32c(x_nhwc), L.f32c(gy_nhwc)
-        L.check(_wgrad_call(x_nhwc, gy_nhwc, offset, N, H, W, Cin, Cout, hit[1], 0, rows), "jdet_conv3x3_wgrad")
-        return None
+        if hit[1] is not None and hit[3] == stream:
+            N, H, W, _ = x_nhwc.shape
+            x_nhwc, gy_nhwc = L.f32c(x_nhwc), L.f32c(gy_nhwc)
+            L.check(_wgrad_call(x_nhwc, gy_nhwc, offset, N, H, W, Cin, Cout, hit[1], 0, rows), "jdet_conv3x3_wgrad")
+            return None
+        # a second tensor goes to the engine, which is free to add the two OUT OF PLACE and release the first use's
+        # buffer: the pointer is dead for the rest of this pass, every later use returns a tensor of its own
+        # (tests/test_gpu_conv_routes.py, case 19/side1: a use on the first stream AFTER one on the side stream added
+        # into memory the allocator had handed out again -- the next data gradient read an overwritten input)
+        _GW_ACC[key] = (tid, None, hit[2], hit[3])
     buf = conv3x3_wgrad_nhwc(x_nhwc, gy_nhwc, offset, rows=rows)
     if tid >= 0 and (_GW_ACC.get(key) is None or _GW_ACC[key][0] != tid):
         _GW_ACC[key] = (tid, buf.data_ptr(), (Cout, Cin, x_nhwc.device), stream)
@@ -499,6 +505,9 @@ def rows_tower(convs, x, flags, rowmask=None):
 
 
 CONV1X1_GEMM = os.environ.get("JDET_CONV1X1_GEMM", "1") == "1"
+# the library's data / weight gradients, called through this one name by both backwards below (tests wrap it to see which
+# gradients a route left to the library: tests/test_gpu_conv_routes.py)
+_convolution_backward = torch.ops.aten.convolution_backward
 
 
 def _is_1x1(x, weight, stride, padding, groups):
@@ -522,8 +531,8 @@ def _conv1x1_backward(g, x, weight, stride, padding, dilation, groups, need):
     if need[1] and N * H * W <= 4096:
         gw1 = (gm.t() @ x.permute(0, 2, 3, 1).reshape(-1, Ci)).view(Co, Ci, 1, 1)
         need[1] = False
-    _, gw, _ = torch.ops.aten.convolution_backward(g, x, weight, None, stride, padding, dilation, False,
-                                                   [0, 0], groups, need) if any(need) else (None, None, None)
+    _, gw, _ = _convolution_backward(g, x, weight, None, stride, padding, dilation, False,
+                                     [0, 0], groups, need) if any(need) else (None, None, None)
     gw = gw1 if gw1 is not None else gw
     if gw is not None and gw.stride() != weight.stride() and gw.numel() == weight.numel():
         # (Cout, Cin, 1, 1) is one memory order under two stride spellings: the parameter's own keeps the
@@ -571,8 +580,7 @@ def _conv_backward(saved, cfg, needs, g):
         gw = shared_wgrad(weight, x.permute(0, 2, 3, 1), g.permute(0, 2, 3, 1))      # (None: added to an earlier use's)
         need[1] = False
     if any(need):
-        lx, lw, _ = torch.ops.aten.convolution_backward(g, x, weight, None, stride, padding, dilation, False, [0, 0],
-                                                        groups, need)
+        lx, lw, _ = _convolution_backward(g, x, weight, None, stride, padding, dilation, False, [0, 0], groups, need)
         gx, gw = (lx if need[0] else gx), (lw if need[1] else gw)
     return gx, gw, gb
 
