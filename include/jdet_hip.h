@@ -706,6 +706,531 @@ int jdet_assign_max_iou(const float* overlaps, int K, int A, float pos_iou_thr, 
                         int32_t* gt_inds, float* max_overlaps, int32_t* labels, void* workspace,
                         size_t workspace_bytes, jdet_stream_t stream);
 
+/* ---- The ATSS assigner (csrc/atss_assign.hip) -------------------------------------------------------------------- */
+/* Most candidates (levels x topk) one gt may have: one wavefront lane per candidate.  The reference config has 5 x 9. */
+#define JDET_ATSS_MAX_CANDIDATES 64
+
+/* ATSSAssignerRbbox.assign (models/boxes/assigner.py:L314-391; points_in_rotated_boxes, boxes/box_ops.py:L725-741) in
+ * three launches, without the (A, K) IoU / distance / inside matrices, the five topk calls, the per-gt loop and the
+ * second "-INF" matrix of the reference: only the K x C candidate pairs are ever evaluated.
+ *
+ *   anchors        (A, anchor_stride >= 5) rows [xc, yc, w, h, theta], all levels concatenated
+ *   level_offsets  HOST pointer, L + 1 ints: level l is the rows [level_offsets[l], level_offsets[l+1]);
+ *                  [0] = 0, non-decreasing, [L] = A
+ *   gt             (K, 5); gt_labels (K) int32 or NULL
+ *   overlaps       NULL: the IoU of a candidate pair is computed in the kernel by the device function
+ *                  jdet_box_iou_rotated uses (version 0, sort_mode 0; argument order (anchor, gt)), bit-equal to
+ *                  that entry point's matrix element.  Non-NULL: an (A, K) row-major matrix the caller computed
+ *                  with any iou_calculator; its values are read instead.  They must be >= 0.
+ *   out            gt_inds (A) int32: 0 or g + 1; max_overlaps (A): the winning IoU, or -1e8f (the reference's
+ *                  -INF, L374) where unassigned; labels (A) int32 or NULL: gt_labels[g], or labels_filled where
+ *                  unassigned (labels != NULL needs gt_labels != NULL).  Every element is written.
+ *
+ * The rules, step by step.  Those the reference leaves open are this project's:
+ *   distance     sqrtf(dx*dx + dy*dy) of the centres in fp32, no contraction (L329-330).
+ *   candidates   per (gt, level) the min(topk, n_level) anchors of smallest distance; equal distances go to the
+ *                LOWER anchor index (Jittor's topk tie order is not pinned by anything; this one is ours).  The
+ *                clamp to n_level is mmdet's (the reference's topk would fail on a level of fewer than topk
+ *                anchors); a level of 0 anchors contributes nothing.  Candidate order: level-major, then rank;
+ *                C = sum_l min(topk, n_l) per gt.
+ *   threshold    mean and unbiased variance (/(C-1), L350-356) summed serially in candidate order in fp32:
+ *                s = 0; s += iou[c]; mean = s / C; v = 0; d = iou[c] - mean; v += d * d; var = v / (C - 1);
+ *                thr = mean + sqrtf(fmaxf(var, 1e-6f)).
+ *   inside       |dx*cos(a) + dy*sin(a)| < w/2 and |-dx*sin(a) + dy*cos(a)| < h/2 with (dx, dy) = anchor centre
+ *                - gt centre and one sincosf per gt.  This is the algebraic form of L734-740, which takes
+ *                r = |(dx, dy)|, phi = atan2(dy, dx) and tests |r cos(phi - a)| < w/2, |r sin(phi - a)| < h/2:
+ *                r cos(phi - a) = dx cos a + dy sin a and r sin(phi - a) = -dx sin a + dy cos a.  The two forms can
+ *                differ only for a centre within rounding of a gt's edge.
+ *   positive     iou >= thr, inside and iou > 0 (thr >= 1e-3 whenever the IoUs are >= 0).
+ *   conflicts    an anchor claimed by several gts goes to the highest IoU, equal IoUs to the LOWER gt index (the
+ *                first index, as jt.argmax).  Resolved by a 64-bit integer atomicMax on a per-anchor key
+ *                (float_bits(iou) << 32) | (0xFFFFFFFF - g): order-independent, hence deterministic; key 0 =
+ *                unassigned.  The keys are cleared by the first launch (no memset node in a captured step).
+ *
+ * Refused before any launch: JDET_E_BADARG for a null anchors / level_offsets / gt / gt_inds / max_overlaps /
+ * workspace pointer, labels without gt_labels, a workspace that is not 8-byte aligned, A <= 0, K <= 0, L <= 0,
+ * topk <= 0, anchor_stride < 5, level_offsets not as above; JDET_E_UNSUPPORTED for L * topk >
+ * JDET_ATSS_MAX_CANDIDATES or C < 2 (the variance divides by C - 1); JDET_E_WORKSPACE for fewer bytes than
+ * jdet_atss_assign_workspace(A, K, L, topk).  The workspace may hold anything. */
+size_t jdet_atss_assign_workspace(int A, int K, int L, int topk);
+int jdet_atss_assign(const float* anchors, int A, int anchor_stride, const int32_t* level_offsets, int L,
+                     const float* gt, int K, const int32_t* gt_labels, const float* overlaps, int topk,
+                     int labels_filled, int32_t* gt_inds, float* max_overlaps, int32_t* labels, void* workspace,
+                     size_t workspace_bytes, jdet_stream_t stream);
+
+/* ---- The row-sparse convolution gradients (csrc/conv_rows.hip) ------------------------------------------------------
+ * What they are for: the regression towers of the S2ANet head (models/roi_heads/s2anet_head.py:L127-205) are trained by
+ * a smooth-L1 loss whose weight is zero for every anchor that is not positive, so the gradient entering their 3x3
+ * convolutions is exactly zero on almost every position row.  The three entry points below compute the same data and
+ * weight gradients as the dense kernels from the non-zero rows only.  No value is read back to the host and no launch
+ * shape depends on device data: the capacity of every list is P = N*H*W rows, so there is no overflow path, and a
+ * fully dense gradient is computed correctly (only slower than by the dense kernels).
+ */
+/* The non-zero rows of a channels-last gradient g (N,H,W,C) = (P, C), in three launches.  Comes before the two
+ * entry points below in place of nothing the reference has: Jittor's autograd runs the dense gradients.
+ *   flags         (P) bytes, every one written: 1 where any element of the row has (bits & 0x7fffffff) != 0 -- rows
+ *                 holding a NaN or an Inf are kept, rows of +0 / -0 are dropped -- else 0
+ *   rows          (P) int32: the flagged positions in ASCENDING order in the entries [0, counts[0]), -1 in the rest
+ *   rows_dilated  (P) int32: ascending positions whose 3x3 neighbourhood (n, y + dy, x + dx), taken inside the same
+ *                 image -- never across a row end or an image boundary -- holds a flagged row, in the entries
+ *                 [0, counts[1]), -1 in the rest
+ *   counts        2 int32: the two list lengths
+ * C % 4 == 0, P * C < 2^30, g 16-byte aligned, else JDET_E_UNSUPPORTED / JDET_E_BADARG.  workspace:
+ * jdet_rows_nonzero_workspace(N, H, W) bytes, 4-byte aligned, may hold anything; fewer bytes: JDET_E_WORKSPACE. */
+size_t jdet_rows_nonzero_workspace(int N, int H, int W);
+int jdet_rows_nonzero(const float* g_nhwc, int N, int H, int W, int C, uint8_t* flags, int32_t* rows,
+                      int32_t* rows_dilated, int32_t* counts, void* workspace, size_t workspace_bytes,
+                      jdet_stream_t stream);
+
+/* Cin % 4 == 0 and Cout % 16 == 0: what both gradient entry points below take (else JDET_E_UNSUPPORTED). */
+int jdet_conv3x3_rows_supported(int Cin, int Cout);
+
+/* gw (Cout,3,3,Cin) += sum over the listed positions r of gy[r, co] * x[nbr(r, tap), ci]; neighbours outside the
+ * image contribute zero.  Replaces jdet_conv3x3_wgrad (plain form) where gy is zero outside rows[0 .. *count): the
+ * same tiles, fragments and float atomics with the K index taken from the list, so several calls may target one
+ * buffer exactly as there.  rows / count: device pointers (jdet_rows_nonzero's `rows` and `counts`); entries past
+ * *count are not read; *count == 0 adds nothing.  The grid is fixed by the channel counts; (P + 16) * max(Cin, Cout)
+ * < 2^30 and 16-byte aligned x / gy, else JDET_E_UNSUPPORTED / JDET_E_BADARG. */
+int jdet_conv3x3_wgrad_rows_workers(int Cin, int Cout); /* K workers per tile: at most this many partial sums are added
+                                                           to one element of gw per call (0: unsupported channels) */
+int jdet_conv3x3_wgrad_rows(const float* x_nhwc, const float* gy_nhwc, const int32_t* rows, const int32_t* count,
+                            int N, int H, int W, int Cin, int Cout, float* gw_krsc, jdet_stream_t stream);
+
+/* gx[r, ci] = sum over taps and co of gy[nbr(r, tap), co] * wd[ci, tap, co] for every r of the list; rows of gx that
+ * are not listed are left alone, or -- zero_first != 0 -- zero-filled by a launch of this call, so that gx
+ * (N,H,W,Cin) is fully written.  Replaces the library's dense data gradient (convolution_backward, igemm_bwd_*) where
+ * gy is zero outside the rows whose dilation the list is (jdet_rows_nonzero's `rows_dilated`, `counts + 1`).  wd
+ * (Cin,3,3,Cout): the flipped weights jdet_conv_dgrad_weights writes.  The grid is fixed by P (P / 64 row tiles);
+ * tiles past *count leave at once.  P * max(Cin, Cout) < 2^30, 16-byte aligned gy / wd, else JDET_E_UNSUPPORTED /
+ * JDET_E_BADARG. */
+int jdet_conv3x3_dgrad_rows(const float* gy_nhwc, const float* wd_crsk, const int32_t* rows, const int32_t* count,
+                            int N, int H, int W, int Cin, int Cout, int zero_first, float* gx_nhwc,
+                            jdet_stream_t stream);
+
+/* ---- The row-sparse convolution forward (csrc/conv_rows.hip) --------------------------------------------------------
+ * What they are for: in training, the output of the S2ANet head's ODM regression tower (models/roi_heads/
+ * s2anet_head.py:L127-205, odm_reg_convs -> odm_reg) is read by the smooth-L1 loss only, and that loss weighs every
+ * anchor that is not positive with 0 (L300-340).  With S0 the positive position rows, the 3x3 prediction layer needs its
+ * input on the 3x3 dilation of S0 and the tower layer before it on the dilation of that: the two entry points below
+ * make those lists from a flag byte per position and compute conv + bias + ReLU on the listed rows only.  No value is
+ * read back to the host and no launch shape depends on device data: every list has capacity P = N*H*W rows, so there is
+ * no overflow path, and a dense list is computed correctly (only slower than by the dense kernel).
+ */
+/* Three ascending row lists from one flag byte per position (non-zero = listed), in four launches (the dilation and
+ * list kernels of jdet_rows_nonzero).  Comes in place of nothing the reference has.
+ *   flags          (P) bytes, read only
+ *   rows           (P) int32: the flagged positions, ascending, in [0, counts[0]); -1 in the rest
+ *   rows_dilated   (P) int32: the positions whose 3x3 neighbourhood (n, y + dy, x + dx), taken inside the same image --
+ *                  never across a row end or an image boundary -- holds a flagged one, in [0, counts[1]); -1 in the rest
+ *   rows_dilated2  (P) int32: the same dilation applied to rows_dilated's set, in [0, counts[2]); -1 in the rest
+ *   counts         3 int32: the three list lengths
+ * P < 2^30, else JDET_E_UNSUPPORTED.  workspace: jdet_rows_from_flags_workspace(N, H, W) bytes, 4-byte aligned, may
+ * hold anything; fewer bytes: JDET_E_WORKSPACE. */
+size_t jdet_rows_from_flags_workspace(int N, int H, int W);
+int jdet_rows_from_flags(const uint8_t* flags, int N, int H, int W, int32_t* rows, int32_t* rows_dilated,
+                         int32_t* rows_dilated2, int32_t* counts, void* workspace, size_t workspace_bytes,
+                         jdet_stream_t stream);
+
+/* Cin % 16 == 0 and Cout % 16 == 0: what the entry point below takes (else JDET_E_UNSUPPORTED). */
+int jdet_conv3x3_rows_forward_supported(int Cin, int Cout);
+
+/* y[r, co] = [relu](sum over taps and ci of x[nbr(r, tap), ci] * w[co, tap, ci] + bias[co]) * rowmask[r] for every r
+ * of the list: 3x3 / stride 1 / pad 1, neighbours outside the image contribute zero.  Replaces
+ * jdet_conv3x3_igemm_forward (plain form) where only the listed rows of y are read: w (Cout,3,3,Cin), bias (Cout) or
+ * null, rowmask (P) or null with that entry point's meaning (a listed row whose mask is 0 is written as 0).  Rows of y
+ * that are not listed are left alone, or -- zero_first != 0 -- zero-filled by a launch of this call, so that y
+ * (N,H,W,Cout) is fully written.  rows / count: device pointers (a list of jdet_rows_from_flags and its count);
+ * entries past *count are not read; *count == 0 computes nothing.  The grid is fixed by P (P / 64 row tiles); tiles past
+ * *count leave at once.  It is the tile of jdet_conv3x3_dgrad_rows with conv_igemm.hip's epilogue.
+ * P * max(Cin, Cout) < 2^30, 16-byte aligned x / w, else JDET_E_UNSUPPORTED / JDET_E_BADARG. */
+int jdet_conv3x3_rows_forward(const float* x_nhwc, const float* w_krsc, const float* bias, int relu,
+                              const float* rowmask, const int32_t* rows, const int32_t* count, int N, int H, int W,
+                              int Cin, int Cout, int zero_first, float* y_nhwc, jdet_stream_t stream);
+
+/* ---- Rotated FCOS: point targets and the polygon IoU loss (csrc/fcos_targets.hip, csrc/poly_iou_loss.hip) -------- */
+/* gts of one image staged in LDS at a time; an image of more gts is walked in chunks of this size, so any K works */
+#define JDET_FCOS_GT_CHUNK 64
+/* most pyramid levels of one call (the reference config has 5) */
+#define JDET_FCOS_MAX_LEVELS 8
+
+/* FCOSHead.get_targets (models/roi_heads/fcos_head.py:L535-670) for all images and all levels in ONE launch, one
+ * thread per (image, point), without the (points x gts) tensors of areas, ranges, offsets, matrices and distances.
+ *
+ *   levels          HOST pointer, L rows of 3 ints (H, W, stride): level l has H * W points, row-major, point (x, y) at
+ *                   (x * stride + stride / 2, y * stride + stride / 2) (integer division, L532); the points of all
+ *                   levels concatenated are the N = sum H * W points of an image
+ *   regress_ranges  HOST pointer, L rows of 2 floats (lo, hi)
+ *   gt              (B, Kmax, 5) rows [xc, yc, w, h, theta]; gt_labels (B, Kmax) int32, 1-based as everywhere here
+ *   gt_count        DEVICE pointer, (B) int32: image b has the gts [0, gt_count[b]) of its Kmax rows (read in the
+ *                   kernel, clamped to [0, Kmax]: no host sync).  Rows beyond it are never read.
+ *   out             labels (B, N) int32: gt_labels - 1 of the winner in 0 .. num_classes - 1, or num_classes
+ *                   (background); bbox_targets (B, N, 5) [l, t, r, b, theta], l..b divided by the level's stride when
+ *                   norm_on_bbox; centerness (B, N): sqrtf(min(l,r)/max(l,r) * (min(t,b)/max(t,b))) of the values
+ *                   written to bbox_targets, 0 for background; gt_inds (B, N) int32 or NULL: the winner's index, -1
+ *                   for background.  Every element is written.
+ *
+ * Each gt is prepared once by the thread that stages it: mintheta_obb (boxes/box_ops.py:L679-692, with its
+ * pi = 3.141592), one sincosf of the resulting angle, the area w * h of the INPUT box, label - 1.  Per (point, gt), in
+ * fp32 without contraction:
+ *   (ox, oy) = point - centre;  rx = cos * ox + (-sin) * oy;  ry = sin * ox + cos * oy      ([cos, -sin; sin, cos], L619)
+ *   l = w/2 + rx, r = w/2 - rx, t = h/2 + ry, b = h/2 - ry
+ *   inside  min(l, t, r, b) > 0; with center_sampling also |rx| < stride * radius and |ry| < stride * radius (L635-649)
+ *   range   max(l, t, r, b) >= lo && max(l, t, r, b) <= hi, inclusive on both sides (L652-655)
+ * The rules the reference leaves open or gets wrong are this project's:
+ *   winner      the smallest area among the gts that pass both tests; equal areas go to the LOWER gt index (the first
+ *               minimum, as an argmin that scans upwards).
+ *   background  a point no gt survives at gets the label num_classes, bbox_targets 0 0 0 0 0, centerness 0 and
+ *               gt_inds -1.  (The reference's argmin over an all-INF row picks gt 0 and keeps its distances; nothing
+ *               reads them.  The general route of FCOSHead.get_targets writes the same zeros.)
+ *   no gts      an image with gt_count == 0 is background everywhere.  (The reference returns label 0 there, L604-606,
+ *               which marks every point as class 0: not reproduced.)
+ *
+ * Refused before any launch: JDET_E_BADARG for a null levels / regress_ranges / gt_count / labels / bbox_targets /
+ * centerness pointer, null gt or gt_labels with Kmax > 0, B <= 0, Kmax < 0, L <= 0, num_classes <= 0, a level with
+ * H, W or stride <= 0, radius <= 0 or not finite with center_sampling; JDET_E_UNSUPPORTED for L > JDET_FCOS_MAX_LEVELS,
+ * B > 65535 or B * N beyond 2^31 - 1. */
+int jdet_fcos_targets(const int32_t* levels, const float* regress_ranges, int L, const float* gt,
+                      const int32_t* gt_labels, const int32_t* gt_count, int B, int Kmax, int num_classes,
+                      int norm_on_bbox, int center_sampling, float radius, int32_t* labels, float* bbox_targets,
+                      float* centerness, int32_t* gt_inds, jdet_stream_t stream);
+
+/* poly_iou_loss (models/losses/poly_iou_loss.py:L39-123) of P box pairs, forward and gradient in ONE launch, one
+ * thread per row.
+ *
+ *   pred, target   (P, 5) rows [xc, yc, w, h, theta]
+ *   weight         (P) or NULL (= 1)
+ *   out            loss (P): weight * (linear ? 1 - iou : -logf(iou)), unreduced; grad_pred (P, 5):
+ *                  d loss[row] / d pred[row], weight included.  The target gets no gradient.
+ *
+ * A row of weight == 0 writes loss 0 and gradient 0 without reading pred or target (they may hold anything, NaN
+ * included), so a dense call over all points does the geometry for the positives only.
+ *
+ * The mathematics is the reference's, line by line, in fp32 without contraction and with IEEE division: obb -> poly as
+ * ops/bbox_transforms.obb2poly; the 16 edge-pair intersections with t = den_t / (num + eps) for the point and the
+ * masks from the plain quotients den_t / num and den_u / num (parallel edges give +-inf or NaN, which compare false);
+ * the two vertex-inside masks by the triangle-area sums against 1e-3 * area; the Graham scan of jdet_convex_sort over
+ * the 24 masked points; the shoelace sum; iou = max(overlap / (a1 + a2 - overlap + eps), eps) with a = w * h.
+ * The gradient is the reverse of exactly that: through the abs of the shoelace sum (sign 0 at 0), through the
+ * gathered hull points (the indices and masks are constants), through t into the pred-side edge endpoints and through
+ * the pred vertices directly, through a1; zero where the clamp is active (overlap / union < eps), so a disjoint pair
+ * gets -log(eps) and gradient 0.
+ *
+ * Refused before any launch: JDET_E_BADARG for P < 0, a null pred / target / loss / grad_pred pointer with P > 0, eps
+ * not > 0.  P == 0 is JDET_OK and launches nothing. */
+int jdet_poly_iou_loss(const float* pred, const float* target, const float* weight, long P, int linear, float eps,
+                       float* loss, float* grad_pred, jdet_stream_t stream);
+
+/* ---- Rotated RepPoints: point assigner, dense convex GIoU loss (csrc/convex_point_assign.hip, convex_giou_loss.hip) */
+/* most points one gt may claim in its level (the reference config uses 1, the assigner's default is 3) */
+#define JDET_CONVEX_ASSIGN_MAX_POS 16
+/* most pyramid levels of one call (the reference config has 5) */
+#define JDET_CONVEX_ASSIGN_MAX_LEVELS 8
+
+/* ConvexAssigner.assign (models/boxes/assigner.py:L433-548) for ALL images of a batch in three launches, instead of
+ * the reference's host loop over the gts of one image (a mask, a gather, a distance tensor, a topk and two scatter
+ * writes per gt).
+ *
+ *   points         (N, point_stride >= 2) rows [x, y, ...], shared by all images, all levels concatenated.  Only
+ *                  columns 0 and 1 are read; the others may hold anything.
+ *   level_offsets  HOST pointer, L + 1 ints: level l is the rows [level_offsets[l], level_offsets[l+1]);
+ *                  [0] = 0, non-decreasing, [L] = N
+ *   level_ids      HOST pointer, L ints: the integer log2(stride) of each level, computed by the caller on the host
+ *                  (the reference's jt.log2(points_stride).int(), L482, applied to exact powers of two).  Distinct.
+ *   gt             (B, Kmax, 8) polygons [x0, y0, .. x3, y3]; gt_labels (B, Kmax) int32 or NULL
+ *   gt_count       DEVICE pointer, (B) int32: image b has the gts [0, gt_count[b]) of its Kmax rows (read in the
+ *                  kernel, clamped to [0, Kmax]: no host sync).  Rows beyond it are never read.
+ *   out            gt_inds (B, N) int32: 0, or g + 1; labels (B, N) int32 or NULL: gt_labels[b][g], or labels_filled
+ *                  where unassigned (labels != NULL needs gt_labels != NULL).  Every element is written.
+ *
+ * The rules, all in fp32 without contraction and with IEEE division and square root:
+ *   box         the horizontal box of a gt is the min / max of its four x and of its four y (L422-431); centre
+ *               (cx, cy) = ((xmin + xmax) / 2, (ymin + ymax) / 2); w = max(xmax - xmin, 1e-6f), h likewise (L489-491).
+ *   level       gt_lvl = (int)((lg(w / scale) + lg(h / scale)) / 2), truncated toward zero as .int() does (L493-494),
+ *               then clamped to [min(level_ids), max(level_ids)] (L495).  lg(x) is log2f(x), except that an exact
+ *               power of two (frexpf gives the mantissa 0.5f) returns its exponent as an exactly converted integer: a
+ *               gt with w / scale and h / scale exact powers of two lands on the mathematically exact level whatever
+ *               the last bit of log2f is.
+ *   distance    sqrtf(dx * dx + dy * dy) with dx = (px - cx) / w, dy = (py - cy) / h (L516).
+ *   candidates  the min(pos_num, n_level) points of smallest distance in the level whose id is gt_lvl; equal
+ *               distances go to the LOWER point index.  The clamp to n_level and the tie rule are this project's (the
+ *               reference's topk fails on a level of fewer than pos_num points, and nothing pins its tie order).
+ *               A gt whose level id equals no entry of level_ids (a gap in the pyramid) claims nothing.
+ *   conflicts   a point claimed by several gts goes to the smallest distance, equal distances to the LOWER gt index:
+ *               exactly what the reference's sequential loop with its strict < (L527) leaves.  Resolved
+ *               order-independently by a 64-bit integer atomicMin on a per-(image, point) key
+ *               (float_bits(distance) << 32) | g; distances are >= 0, so their bit patterns order as integers; the
+ *               key ~0 = unclaimed.  The keys are cleared by the first launch (no memset node in a captured step).
+ *   no gts      an image with gt_count == 0 writes gt_inds 0 and labels_filled everywhere.  (The reference returns
+ *               labels -1 there, L474-476; its caller never reads them.)
+ * Launches: clear the keys; one wavefront per (image, gt) finds its candidates -- rank r is the smallest packed key
+ * (distance bits << 32 | point index) above rank r - 1's, by a wave-wide 64-bit minimum over the recomputed
+ * distances of the level -- and claims them; one lane per (image, point) turns its key into gt_inds / labels.
+ *
+ * Refused before any launch: JDET_E_BADARG for a null points / level_offsets / level_ids / gt_count / gt_inds /
+ * workspace pointer, a null gt with Kmax > 0, labels without gt_labels, a workspace that is not 8-byte aligned,
+ * N <= 0, B <= 0, Kmax < 0, L <= 0, point_stride < 2, pos_num <= 0, scale not > 0 or not finite, level_offsets not as
+ * above, two equal level_ids; JDET_E_UNSUPPORTED for L > JDET_CONVEX_ASSIGN_MAX_LEVELS, pos_num >
+ * JDET_CONVEX_ASSIGN_MAX_POS, B > 65535, B * N or B * Kmax beyond 2^31 - 1; JDET_E_WORKSPACE for fewer bytes than
+ * jdet_convex_point_assign_workspace(B, N) (0 for B <= 0 or N <= 0).  The workspace may hold anything. */
+size_t jdet_convex_point_assign_workspace(int B, int N);
+int jdet_convex_point_assign(const float* points, int N, int point_stride, const int32_t* level_offsets,
+                             const int32_t* level_ids, int L, const float* gt, const int32_t* gt_labels,
+                             const int32_t* gt_count, int B, int Kmax, float scale, int pos_num, int labels_filled,
+                             int32_t* gt_inds, int32_t* labels, void* workspace, size_t workspace_bytes,
+                             jdet_stream_t stream);
+
+/* ConvexGIoULossFunction.execute (models/losses/convex_giou_loss.py:L10-53) of P aligned (point set, polygon) rows in
+ * its dense form: forward and gradient in ONE launch over ALL rows, the positives marked by their weight, so the step
+ * has no nonzero() host round trip.  Half a wavefront per row, the dual-number evaluation of jdet_convex_giou
+ * (csrc/convex_giou.h): the GIoU and its 18 derivatives of a row are bit-equal to that entry point's on the same
+ * normalised operands.
+ *
+ *   pred     (P, 18) decoded points [x0, y0, .. x8, y8];  target (P, 8) polygons;  weight (P);  norm (P), the
+ *            normalize_term = point_base_scale * stride of each row (rotated_reppoints_head.py:L598, L620-622)
+ *   out      loss (P): weight * (1 - giou), unreduced;  grad_pred (P, 18): d loss[row] / d pred[row]
+ *
+ * Per row, in fp32 with IEEE division:
+ *   p = pred / norm, t = target / norm                    (both operands are divided, L620-622)
+ *   giou, g[18] = the GIoU of (p, t) and its raw gradient w.r.t. the NORMALISED points p, rounded to fp32
+ *   loss = (1 - giou) * weight                            (L33-35)
+ *   g = g * weight                                        (L36)
+ *   THEN a row with any component g[k] > 1 has all 18 components set to 1e-6f   (L47-48)
+ *   then g = -g                                           (L51)
+ *   then grad_pred = g / norm                             (the chain rule through p = pred / norm)
+ * avg_factor, loss_weight and the incoming gradient are NOT applied here: the autograd node multiplies by them from
+ * device scalars.
+ * A row of weight == 0 writes loss 0 and gradient 0 without reading pred, target or norm (they may hold anything,
+ * NaN included): the rule of jdet_poly_iou_loss.
+ *
+ * Refused before any launch: JDET_E_BADARG for P < 0, a null pred / target / weight / norm / loss / grad_pred pointer
+ * with P > 0; JDET_E_UNSUPPORTED for P beyond 2^32 - 2.  P == 0 is JDET_OK and launches nothing. */
+int jdet_convex_giou_loss(const float* pred, const float* target, const float* weight, const float* norm, long P,
+                          float* loss, float* grad_pred, jdet_stream_t stream);
+
+/* ---- H2RBox: the rotated second view and the view-consistency loss (csrc/rotate_crop.hip, h2rbox_aug_loss.hip) ---- */
+/* padding modes of jdet_rotate_crop (the order of torch.nn.functional.grid_sample's) */
+#define JDET_PAD_ZEROS 0
+#define JDET_PAD_BORDER 1
+#define JDET_PAD_REFLECTION 2
+/* most rotation-agnostic classes of one jdet_h2rbox_aug_loss_forward call */
+#define JDET_H2RBOX_MAX_AGNOSTIC 16
+
+/* H2RBox.rotate_crop (models/networks/h2rbox.py:L35-75) of an image batch in ONE launch: only the out_h x out_w window
+ * that survives the centre crop is computed, the (n, h, w, 2) grid never exists.  Forward only (images carry no
+ * gradient).
+ *
+ *   img      (N, C, H, W) fp32, NCHW
+ *   out      (N, C, out_h, out_w) fp32; every element is written
+ *   cos_t, sin_t   cos / sin of the angle, computed on the host in double and rounded to float (the reference stores
+ *            math.cos / math.sin in a float tensor, L42-43)
+ *
+ * Per output pixel (n, y, x), the same coordinates for all C channels:
+ *   (X, Y)   = (x + (W - out_w) / 2, y + (H - out_h) / 2)                     (integer division: the crop offset, L39-40)
+ *   (gx, gy) = (-1 + 2 X / (W - 1), -1 + 2 Y / (H - 1))                       (linspace(-1, 1, .), L45-46)
+ *   (sx, sy) = (gx * cos + gy * sin, -gx * sin + gy * cos)                    (row vector times [[cos, -sin], [sin, cos]],
+ *                                                                              L43-49; no isometry when H != W: kept)
+ *   (ix, iy) = ((sx + 1) / 2 * (W - 1), (sy + 1) / 2 * (H - 1))               (align_corners = True)
+ *   padding  reflection about 0 and size - 1 followed by a clip to [0, size - 1]; border: that clip alone; zeros: a
+ *            corner outside the frame contributes 0
+ *   value    bilinear over the four corners floor(ix), floor(ix) + 1, floor(iy), floor(iy) + 1, as grid_sample
+ * The coordinates are computed in double (a dozen operations per pixel, shared by the channels), the interpolation in
+ * fp32.  cos_t == 1 && sin_t == 0 (theta == 0) is a bit-exact cropped copy: the reference skips the sampling there.
+ *
+ * Refused before any launch: JDET_E_BADARG for a null img / out, N, C, out_h or out_w <= 0, H < 2 or W < 2,
+ * out_h > H or out_w > W, an unknown padding mode, cos_t or sin_t not finite; JDET_E_UNSUPPORTED for N > 65535 or
+ * N * C * H * W beyond 2^31 - 1. */
+int jdet_rotate_crop(const float* img, int N, int C, int H, int W, int out_h, int out_w, float cos_t, float sin_t,
+                     int padding, float* out, jdet_stream_t stream);
+
+/* The consistency branch of H2RBoxHead.loss (models/roi_heads/h2rbox_head.py:L399-506) with H2RBoxLoss.execute
+ * (models/losses/h2rbox_loss.py:L42-66), dense over all B * N points in the image-major order jdet_fcos_targets writes,
+ * one thread per view-1 point, ONE launch.
+ *
+ *   levels        HOST pointer, L rows of 3 ints (H, W, stride), as for jdet_fcos_targets: N = sum H * W
+ *   pred          (B, N, 5) rows [l, t, r, b, theta] of view 1, as the head emits them
+ *   pred_aug      (B, N, 5) the same of view 2 (the rotated view)
+ *   weight        (B, N) the centerness targets; a row takes part when weight > 0
+ *   labels        (B, N) int32 as jdet_fcos_targets writes them (0-based), or NULL when n_agnostic == 0
+ *   agnostic      HOST pointer, n_agnostic 1-BASED class ids (the reference compares rotation_agnostic_classes with
+ *                 labels + 1, L387/L440/L487-491), or NULL when n_agnostic == 0
+ *   rot, cos_r, sin_r   the angle of view 2 and its cos / sin computed on the host in double, rounded to float
+ *   crop_h, crop_w      the size of both views in pixels
+ *   shape_weight, angle_weight   loss_weight of H2RBoxLoss's shape_loss and angle_loss (1 and 1 in the config)
+ *   eps           the clamp of the IoU and of its union (1e-6 in the reference)
+ *   out           terms (B, N, 4): [centre, branch 1, branch 2, weight] of a valid row, zeros otherwise;
+ *                 aug_index (B, N) int32: the view-2 point, in 0 .. N - 1 of the same image, of a valid row, -1
+ *                 otherwise.  Every element is written.
+ *
+ * Cell map.  A row with weight > 0 at cell (x, y) of a level (h, w) goes to
+ *   (xa, ya) = round(((x, y) - ctr) . [[cos, sin], [-sin, cos]] + ctr),  ctr = ((w - 1) / 2, (h - 1) / 2)
+ * i.e. xa = round(dx * cos + dy * (-sin) + cx), ya = round(dx * sin + dy * cos + cy), in fp32 without contraction.
+ * TIE RULE: round is round-half-to-EVEN (rintf, torch.round); both Python routes follow it.  The row is VALID when
+ * 0 <= xa < w and 0 <= ya < h; its view-2 point is off[level] + ya * w + xa.
+ *
+ * A valid row decodes both predictions with distance2obb (boxes/box_ops.py:L694-707, regular_obb included) at their
+ * own points (x * stride + stride / 2, y * stride + stride / 2).  The TARGET is view 1's decoded box [cx, cy, w, h, a]
+ * with (cx, cy) turned about ((crop_w - 1) / 2, (crop_h - 1) / 2) by the same matrix, w and h kept, and the angle
+ * a + rot, times 0 for a rotation-agnostic row (_process_rotation_agnostic(dim=None), L312-319).  With P the decoded
+ * view-2 box, da = P.a - T.a and iou(.) of bbox_overlaps(is_aligned=True) (its max(union, eps) included) clamped
+ * below by eps:
+ *   centre    weight * (|P.cx - T.cx| + |P.cy - T.cy|)
+ *   branch 1  weight * (shape_weight * -log(iou([-w, -h, w, h] of P, the same of T)) + angle_weight * |sin da|)
+ *   branch 2  the same with P's w and h swapped and |cos da|
+ * Rows of weight <= 0 and invalid rows read neither prediction (NaN there is harmless).
+ * The cell map is fp32 (so that the fp32 tensor program decides as the kernel does); a row's arithmetic after it runs
+ * in double and is rounded once on output.
+ *
+ * The scalar minimum of the reference is the caller's: H2RBoxLoss reduces each sub-loss before jt.minimum, so the loss
+ * is loss_weight * (w_c * sum centre + min(sum branch 1, sum branch 2)) / max(sum terms[..., 3], 1) -- NOT a per-row
+ * minimum.
+ *
+ * Refused before any launch: JDET_E_BADARG for a null levels / pred / pred_aug / weight / terms / aug_index, B <= 0,
+ * L <= 0, a level with H, W or stride <= 0, crop_h or crop_w <= 0, n_agnostic < 0, n_agnostic > 0 with a null labels
+ * or agnostic, eps not > 0, rot / cos_r / sin_r / shape_weight / angle_weight not finite; JDET_E_UNSUPPORTED for
+ * L > JDET_FCOS_MAX_LEVELS, n_agnostic > JDET_H2RBOX_MAX_AGNOSTIC, B > 65535 or B * N * 5 beyond 2^31 - 1. */
+int jdet_h2rbox_aug_loss_forward(const int32_t* levels, int L, const float* pred, const float* pred_aug,
+                                 const float* weight, const int32_t* labels, const int32_t* agnostic, int n_agnostic,
+                                 int B, float rot, float cos_r, float sin_r, int crop_h, int crop_w, float shape_weight,
+                                 float angle_weight, float eps, float* terms, int32_t* aug_index,
+                                 jdet_stream_t stream);
+
+/* The gradient of  scale_centre * sum centre + scale_branch * sum branch[*branch]  of the forward above, TWO launches.
+ *
+ *   (levels .. eps)   as the forward's
+ *   aug_index     (B, N) int32, the forward's output
+ *   branch        DEVICE pointer, one int32: 0 selects branch 1, anything else branch 2 (the scalar minimum taken on
+ *                 the device); the other branch contributes nothing
+ *   scale_centre, scale_branch   DEVICE pointers, one float each: the upstream scales
+ *                 (grad_out * loss_weight * w_c / avg and grad_out * loss_weight / avg)
+ *   out           grad_pred (B, N, 5), grad_pred_aug (B, N, 5); every element is written.
+ *
+ * The view-1 side is NOT detached (the reference builds the target from pos_decoded_bbox_preds, L480-494): gradient
+ * flows into both views.  regular_obb's swap and floor-mod pass gradient with factor 1; abs has gradient 0 at 0, as in
+ * autograd.  At the exact ties of the piecewise pieces the kernel's rule is its own and DIFFERS from autograd's: where
+ * the prediction's and the target's half-extent are equal (pw == tw or ph == th) the whole gradient of the min / max
+ * goes to the TARGET's side (torch.minimum / torch.maximum split it evenly there), and a union or IoU exactly at eps
+ * counts as clamped, gradient 0 (torch.clamp passes the gradient at equality).  Away from ties the two agree; the
+ * test fixtures keep every such quantity at least 1e-3 from its tie, so nothing pins the tie rule.
+ *
+ * Several view-1 rows may share a view-2 point.  Launch 1, one thread per view-1 point p, writes grad_pred[p] and its
+ * contribution to its view-2 point into row p of a scratch the caller provides (contrib).  Launch 2, one thread per
+ * view-2 point q, sums the rows p with aug_index[p] == q among the 3 x 3 cells around round(R^-1 (q - ctr) + ctr) in
+ * ascending p (if round(R (p - ctr) + ctr) == q then |p - R^-1 (q - ctr) - ctr| <= sqrt(2) / 2 per coordinate, so p
+ * lies in that block): no floating-point atomics, a fixed summation order, bit-identical runs.
+ *
+ *   contrib       (B, N, 5) fp32 scratch, fully overwritten
+ *
+ * Refused as the forward, and JDET_E_BADARG for a null aug_index / branch / scale_centre / scale_branch / grad_pred /
+ * grad_pred_aug / contrib. */
+int jdet_h2rbox_aug_loss_backward(const int32_t* levels, int L, const float* pred, const float* pred_aug,
+                                  const float* weight, const int32_t* labels, const int32_t* agnostic, int n_agnostic,
+                                  int B, float rot, float cos_r, float sin_r, int crop_h, int crop_w,
+                                  float shape_weight, float angle_weight, float eps, const int32_t* aug_index,
+                                  const int32_t* branch, const float* scale_centre, const float* scale_branch,
+                                  float* grad_pred, float* grad_pred_aug, float* contrib, jdet_stream_t stream);
+
+/* ---- Localization distillation (csrc/dist_loss.hip) -----------------------------------------------------------------
+ * Common to all four (csrc/dist_loss.hip, csrc/dist_softmax.h):
+ *   - every tensor is fp32; logits are contiguous row-major; a row of K <= JDET_DIST_MAX_BINS values is one softmax;
+ *   - a row's arithmetic (max-subtracted softmax in the log-softmax form, the integral, the loss term, the gradient)
+ *     runs in double and is rounded once on output; sums are double, two stages in a fixed order (csrc/reduce.h), no
+ *     floating-point atomics: two runs give the same bits;
+ *   - targets / weights sit behind the blocked row index of jdet_smooth_l1_loss_level: logical row r lives at
+ *     (r / rows_per_block) * block_stride + r % rows_per_block, so a level's window [:, s:e] of the per-image arrays
+ *     is read in place;
+ *   - `workspace` is the one of jdet_sigmoid_focal_loss_workspace().
+ */
+/* most values of one softmax row: reg_max + 1 of the distribution heads, K of the KL divergence */
+#define JDET_DIST_MAX_BINS 32
+
+/* box_ops.integral / integral_angle (models/boxes/box_ops.py:L709-723) of all five sides in ONE launch.  Forward only.
+ *
+ *   logits   (rows, 5 * (reg_max + 1)): side s of a row is the reg_max + 1 values from s * (reg_max + 1) on
+ *   deltas   (rows, 5); every element is written
+ *   delta[r, s] = sum_k softmax(side s of row r)_k * e_k,  e_k = lo + k * ((hi - lo) / reg_max) evaluated in fp32
+ *   with (lo, hi) for the sides s < 4 and (lo_angle, hi_angle) for s == 4: (-2, 2) and (-5, 2) in the reference.
+ *
+ * Refused before any launch: JDET_E_BADARG for rows < 0, reg_max < 1, an end that is not finite, a null logits /
+ * deltas with rows > 0; JDET_E_UNSUPPORTED for reg_max + 1 > JDET_DIST_MAX_BINS.  rows == 0 is a success. */
+int jdet_dist_integral(const float* logits, long rows, int reg_max, float lo, float hi, float lo_angle, float hi_angle,
+                       float* deltas, jdet_stream_t stream);
+
+/* The integral above followed by the weighted L1 / smooth-L1 of one pyramid level as ONE node, TWO launches.
+ *
+ *   logits       as above
+ *   target, weight   (rows, 5) behind blocked row indices (rows of 5 contiguous values); weight may be NULL (ones)
+ *   beta         0: L1; otherwise smooth-L1, |d| < beta ? 0.5 d^2 / beta : |d| - 0.5 beta
+ *   avg_factor   DEVICE pointer, one float
+ *   loss         one float: (sum_{r,s} w * l(E - t) / *avg_factor) * loss_weight, E = delta[r, s] of the integral
+ *   grad_logits  (rows, 5 * (reg_max + 1)), the UNIT gradient d sum / d logits = w * l'(E - t) * p_k * (e_k - E); every
+ *                element is written.  Backward is jdet_loss_grad_scale of it.
+ *
+ * An element of weight 0 contributes nothing and gets gradient 0, whatever its logits and target hold (NaN included);
+ * the target of such an element is not read, and no 16-byte piece of logits that lies wholly in rows whose five weights
+ * are all 0 is read.
+ *
+ * Refused before any launch: JDET_E_BADARG for rows < 0, reg_max < 1, beta < 0 or not finite, an end that is not
+ * finite, a null loss, and with rows > 0 a null logits / target / avg_factor / grad_logits / workspace or a window
+ * with rows_per_block <= 0 or block_stride < 0; JDET_E_UNSUPPORTED for reg_max + 1 > JDET_DIST_MAX_BINS;
+ * JDET_E_WORKSPACE for a short workspace.  rows == 0 is a success with *loss = 0. */
+int jdet_dist_bbox_loss_level(const float* logits, const float* target, long target_rows_per_block,
+                              long target_block_stride, const float* weight, long weight_rows_per_block,
+                              long weight_block_stride, long rows, int reg_max, float lo, float hi, float lo_angle,
+                              float hi_angle, float beta, const float* avg_factor, float loss_weight, float* loss,
+                              float* grad_logits, void* workspace, size_t workspace_bytes, jdet_stream_t stream);
+
+/* knowledge_distillation_kl_div_loss (models/losses/kd_loss.py:L7-39) of one level, the mean over ALL elements of
+ * KLDivLoss's default reduction included.  THREE launches with a weight, TWO without.
+ *
+ *   pred, soft   (M, K) student and teacher logits
+ *   weight       M floats behind a blocked index (rows of ONE value), or NULL
+ *   T            the temperature, >= 1
+ *   sel   = the rows with weight > 0; every row when weight is NULL -- and every row when NO weight is > 0 (the
+ *           reference falls through to the full maps there; levels without a positive anchor are routine)
+ *   count = |sel|, written to *count (one int32 on the device; the backward reads it, the host never does)
+ *   loss  = ((sum_{r in sel} sum_k t_k (log t_k - log p_k)) / float(count * K)) * (T * T) * loss_weight
+ *           with p = softmax(pred_r / T), t = softmax(soft_r / T)
+ * No 16-byte piece of pred / soft that lies wholly in unselected rows is read.
+ *
+ * Refused before any launch: JDET_E_BADARG for M < 0, K < 1, T not >= 1 or not finite, a null loss / count, and with
+ * M > 0 a null pred / soft / workspace or a bad weight window; JDET_E_UNSUPPORTED for K > JDET_DIST_MAX_BINS or
+ * M > 2^31 - 1; JDET_E_WORKSPACE for a short workspace.  M == 0 is a success with
+ * *loss = 0 and *count = 0. */
+int jdet_kd_kl_div_level_forward(const float* pred, const float* soft, const float* weight, long weight_rows_per_block,
+                                 long weight_block_stride, long M, int K, float T, float loss_weight, float* loss,
+                                 int32_t* count, void* workspace, size_t workspace_bytes, jdet_stream_t stream);
+
+/* The gradient of the loss above with respect to pred, ONE launch; both softmaxes are recomputed.
+ *
+ *   count        the forward's output (DEVICE pointer); count == M selects every row
+ *   grad_out     DEVICE pointer, one float: the upstream gradient
+ *   grad_pred    (M, K): grad_out * loss_weight * T * (p_j - t_j) / float(count * K) on selected rows, 0 elsewhere;
+ *                every element is written
+ *
+ * Refused as the forward (no workspace), and JDET_E_BADARG for a null count / grad_out, or a null grad_pred with M > 0. */
+int jdet_kd_kl_div_level_backward(const float* pred, const float* soft, const float* weight, long weight_rows_per_block,
+                                  long weight_block_stride, long M, int K, float T, float loss_weight,
+                                  const int32_t* count, const float* grad_out, float* grad_pred, jdet_stream_t stream);
+
+/* ---- The 3x3 convolution forward on bf16 MFMA through an exact three-way fp32 split (csrc/conv_bf16x3.hip) ----------
+ * Numerics: every fp32 input and weight x is split by truncation into three bf16 values a1 + a2 + a3 == x (exactly);
+ * six bf16 products per operand pair (a3b1, a1b3, a2b2, a2b1, a1b2, a1b1, small terms first within a 16-deep K block)
+ * go into one fp32 accumulator per output.  The result is as close to the exact sum as an fp32 fma chain's (the bound of
+ * jdet_conv3x3_igemm_forward's tests holds with the same headroom), but not bit-equal to that kernel's.  Non-finite
+ * inputs give non-finite outputs, possibly NaN where jdet_conv3x3_igemm_forward gives Inf (Inf splits into Inf, NaN, NaN).
+ */
+/* Cin % 32 == 0, any Cout > 0: what the entry point below takes (else JDET_E_UNSUPPORTED). */
+int jdet_conv3x3_bf16x3_supported(int Cin, int Cout);
+
+/* y[m, co] = [relu](sum over taps and ci of x[nbr(m, tap), ci] * w[co, tap, ci] + bias[co]) * rowmask[m]: 3x3 / stride 1 /
+ * pad 1, channels last, neighbours outside the image contribute zero.  The plain form of jdet_conv3x3_igemm_forward
+ * with that entry point's arguments: x (N,H,W,Cin), w (Cout,3,3,Cin), bias (Cout) or null, rowmask (N*H*W) or null, y
+ * (N,H,W,Cout), every element written.  One launch of 128 x 128 output tiles, no workspace, nothing read back, no launch
+ * shape taken from device data.  N == 0 is a no-op.  x and w 16-byte aligned, y 4-byte aligned (else JDET_E_BADARG);
+ * N*H*W * max(Cin, Cout) < 2^30 and Cout * 9 * Cin < 2^30 (else JDET_E_UNSUPPORTED). */
+int jdet_conv3x3_bf16x3_forward(const float* x_nhwc, int N, int H, int W, int Cin, const float* w_krsc, int Cout,
+                                const float* bias, int relu, const float* rowmask, float* y_nhwc, jdet_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

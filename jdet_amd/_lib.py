@@ -44,8 +44,9 @@ GD_FUNS = {"none": 0, "": 0, None: 0, "log1p": 1, "sqrt": 2, "ln": 3, "exp": 4}
 
 EPI_FORWARD, EPI_ADD, EPI_MASK = 0, 1, 2
 
-# name -> (restype, argtypes); mirrors include/jdet_hip.h one to one (tests/test_abi.py checks it)
+# name -> (restype, argtypes); mirrors include/jdet_hip.h one to one, in its order (tests/test_abi.py checks it)
 SIGNATURES = {
+    # RoIAlign, IoU / NMS, deformable sampling, the MFMA convolutions, losses, head glue, codecs, targets, assigners
     "jdet_version": (_i, []),
     "jdet_nchw_to_nhwc": (_i, [_p, _i, _i, _i, _i, _p, _p]),
     "jdet_nhwc_to_nchw": (_i, [_p, _i, _i, _i, _i, _p, _p]),
@@ -55,30 +56,17 @@ SIGNATURES = {
     "jdet_roi_align_forward_cl": (_i, [_i, _p, _i, _i, _i, _i, _p, _i, _i, _i, _f, _i, _i, _p, _p, _sz, _p]),
     "jdet_roi_align_forward_reference": (_i, [_i, _p, _i, _i, _i, _i, _p, _i, _i, _i, _f, _i, _i, _p, _p, _p]),
     "jdet_roi_align_forward_cl_reference": (_i, [_i, _p, _i, _i, _i, _i, _p, _i, _i, _i, _f, _i, _i, _p, _p, _sz, _p]),
-    "jdet_roi_align_backward_cl": (_i, [_i, _p, _p, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i, _p, _p, _sz, _i, _p]),
+    "jdet_roi_spatial_order": (_i, [_p, _i, _i, _f, _i, _i, _i, _p, _p, _p]),
+    "jdet_roi_align_backward_workspace": (_sz, [_i] * 9),
+    "jdet_roi_align_backward": (_i, [_i, _p, _p, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i, _p, _p, _p, _sz, _p]),
     "jdet_roi_align_backward_clean_bytes": (_sz, [_i] * 9),
+    "jdet_roi_align_backward_cl": (_i, [_i, _p, _p, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i, _p, _p, _sz, _i, _p]),
     "jdet_roi_align_backward_plan_bytes": (_sz, [_i] * 8),
     "jdet_roi_align_backward_plan": (_i, [_i, _p, _i, _i, _i, _i, _i, _i, _f, _i, _p, _sz, _p]),
     "jdet_roi_align_backward_cl_planned": (_i, [_i, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _sz, _p]),
-    "jdet_roi_align_backward_workspace": (_sz, [_i] * 9),
-    "jdet_roi_align_backward": (_i, [_i, _p, _p, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i, _p, _p, _p, _sz, _p]),
-    "jdet_roi_spatial_order": (_i, [_p, _i, _i, _f, _i, _i, _i, _p, _p, _p]),
     "jdet_box_iou_rotated": (_i, [_p, _i, _p, _i, _i, _i, _i, _p, _p]),
     "jdet_nms_rotated_workspace": (_sz, [_i]),
     "jdet_nms_rotated": (_i, [_p, _i, _i, _p, _f, _i, _i, _p, _p, _sz, _p]),
-    "jdet_upsample_add_nhwc_forward": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _f, _p, _p]),
-    "jdet_upsample_add_nhwc_backward": (_i, [_p, _i, _i, _i, _i, _i, _i, _f, _p, _p]),
-    "jdet_zero_fill": (_i, [_p, _sz, _p]),
-    "jdet_graph_replace_memset_nodes": (_i, [_p, ctypes.POINTER(ctypes.c_int)]),
-    "jdet_sum_squares_workspace": (_sz, []),
-    "jdet_sum_squares": (_i, [_p, _sz, _i, _p, _p, _sz, _p]),
-    "jdet_normalize_u8_nhwc": (_i, [_p, _p, _i, _i, _i, _p, _p, _i, _p, _p]),
-    "jdet_feature_refine_forward": (_i, [_p, _p, _i, _i, _i, _i, _f, _i, _p, _p]),
-    "jdet_feature_refine_backward_workspace": (_sz, [_i] * 5),
-    "jdet_feature_refine_backward": (_i, [_p, _p, _i, _i, _i, _i, _f, _i, _p, _p, _sz, _p]),
-    "jdet_poly_iou": (_i, [_p, _i, _i, _p, _i, _i, _i, _p, _p]),
-    "jdet_nms_poly": (_i, [_p, _i, _i, _p, _f, _i, _p, _p, _sz, _p]),
-    "jdet_bbox_overlaps_hbb": (_i, [_p, _i, _p, _i, _i, _i, _i, _f, _p, _p, _p]),
     "jdet_nms_labeled": (_i, [_p, _i, _i, _p, _f, _i, _i, _i, _i, _p, _p, _sz, _p]),
     "jdet_deform_im2col": (_i, [_p, _p] + [_i] * 13 + [_p, _p]),
     "jdet_deform_col2im": (_i, [_p, _p] + [_i] * 13 + [_p, _p]),
@@ -91,10 +79,6 @@ SIGNATURES = {
     "jdet_deform_im2col_nhwc": (_i, [_p, _p] + [_i] * 12 + [_p, _p]),
     "jdet_deform_col2im_nhwc_workspace": (_sz, [_i] * 12),
     "jdet_deform_col2im_nhwc": (_i, [_p, _p] + [_i] * 12 + [_p, _p, _sz, _p]),
-    "jdet_convex_iou": (_i, [_p, _i, _p, _i, _p, _p]),
-    "jdet_convex_giou": (_i, [_p, _p, _i, _p, _p]),
-    "jdet_min_area_bbox": (_i, [_p, _i, _p, _p]),
-    "jdet_convex_sort": (_i, [_p, _p, _i, _i, _i, _p, _p]),
     "jdet_conv3x3_igemm_supported": (_i, [_i, _i]),
     "jdet_conv3x3_igemm_forward": (_i, [_p, _i, _i, _i, _i, _p, _i, _p, _i, _p, _p, _i, _p, _p, _sz, _p]),
     "jdet_conv3x3_igemm_workspace": (_sz, [_i] * 5),
@@ -109,6 +93,10 @@ SIGNATURES = {
     "jdet_bn_act_backward_from_output_rows": (_sz, [_l, _i]),
     "jdet_bn_act_backward_from_output": (_i, [_p, _p, _p, _p, _l, _i, _p, _p, _p, _p, _f, _p, _p, _sz, _p]),
     "jdet_bn_sums_finish": (_i, [ctypes.POINTER(BnSumsJob), _i, _p]),
+    "jdet_convex_iou": (_i, [_p, _i, _p, _i, _p, _p]),
+    "jdet_convex_giou": (_i, [_p, _p, _i, _p, _p]),
+    "jdet_min_area_bbox": (_i, [_p, _i, _p, _p]),
+    "jdet_convex_sort": (_i, [_p, _p, _i, _i, _i, _p, _p]),
     "jdet_sigmoid_focal_loss_workspace": (_sz, []),
     "jdet_sigmoid_focal_loss": (_i, [_p, _p, _p, _l, _i, _f, _f, _p, _p, _p, _sz, _p]),
     "jdet_smooth_l1_loss": (_i, [_p, _p, _p, _l, _f, _p, _p, _p, _sz, _p]),
@@ -125,6 +113,10 @@ SIGNATURES = {
     "jdet_bias_act_backward": (_i, [_p, _p, _l, _i, _i, _p, _p, _p, _sz, _p]),
     "jdet_channel_sum_workspace": (_sz, [_l, _i]),
     "jdet_channel_sum": (_i, [_p, _l, _i, _p, _p, _sz, _p]),
+    "jdet_zero_fill": (_i, [_p, _sz, _p]),
+    "jdet_graph_replace_memset_nodes": (_i, [_p, ctypes.POINTER(ctypes.c_int)]),
+    "jdet_sum_squares_workspace": (_sz, []),
+    "jdet_sum_squares": (_i, [_p, _sz, _i, _p, _p, _sz, _p]),
     "jdet_arf_forward": (_i, [_p, _p] + [_i] * 6 + [_p, _p]),
     "jdet_arf_backward": (_i, [_p, _p] + [_i] * 6 + [_p, _p]),
     "jdet_arf_forward_cl": (_i, [_p, _p] + [_i] * 6 + [_p, _p]),
@@ -144,73 +136,50 @@ SIGNATURES = {
     "jdet_anchor_targets_rotated": (_i, [_p, _p, _p, _p, _i, _i, _p, _p, _f, _p, _p, _p, _p, _p, _p]),
     "jdet_anchor_targets_rotated_boxes": (_i, [_p, _p, _p, _i, _i, _f, _p, _p, _p, _p, _p, _p]),
     "jdet_obb2hbb2obb": (_i, [_p, _i, _i, _p, _p]),
+    "jdet_upsample_add_nhwc_forward": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _f, _p, _p]),
+    "jdet_upsample_add_nhwc_backward": (_i, [_p, _i, _i, _i, _i, _i, _i, _f, _p, _p]),
+    "jdet_normalize_u8_nhwc": (_i, [_p, _p, _i, _i, _i, _p, _p, _i, _p, _p]),
+    "jdet_feature_refine_forward": (_i, [_p, _p, _i, _i, _i, _i, _f, _i, _p, _p]),
+    "jdet_feature_refine_backward_workspace": (_sz, [_i] * 5),
+    "jdet_feature_refine_backward": (_i, [_p, _p, _i, _i, _i, _i, _f, _i, _p, _p, _sz, _p]),
+    "jdet_poly_iou": (_i, [_p, _i, _i, _p, _i, _i, _i, _p, _p]),
+    "jdet_nms_poly": (_i, [_p, _i, _i, _p, _f, _i, _p, _p, _sz, _p]),
+    "jdet_bbox_overlaps_hbb": (_i, [_p, _i, _p, _i, _i, _i, _i, _f, _p, _p, _p]),
     "jdet_assign_max_iou_workspace": (_sz, [_i]),
     "jdet_assign_max_iou": (_i, [_p, _i, _i, _f, _f, _f, _f, _i, _i, _p, _i, _p, _p, _p, _p, _sz, _p]),
-}
-
-# include/jdet_hip_atss.h (same library; a table of its own until the contract table of tests/abi_cases.py is next
-# revised -- the header says why; tests/test_atss_cpu.py checks it against the header and the exports)
-ATSS_SIGNATURES = {
+    # the ATSS assigner
     "jdet_atss_assign_workspace": (_sz, [_i, _i, _i, _i]),
     "jdet_atss_assign": (_i, [_p, _i, _i, _p, _i, _p, _i, _p, _p, _i, _i, _p, _p, _p, _p, _sz, _p]),
-}
-
-# include/jdet_hip_rows.h (csrc/conv_rows.hip; same library, a table of its own for the reason ATSS_SIGNATURES has one;
-# tests/test_conv_rows_cpu.py checks it against the header and the exports)
-ROWS_SIGNATURES = {
+    # the row-sparse convolution gradients
     "jdet_rows_nonzero_workspace": (_sz, [_i, _i, _i]),
     "jdet_rows_nonzero": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _sz, _p]),
     "jdet_conv3x3_rows_supported": (_i, [_i, _i]),
     "jdet_conv3x3_wgrad_rows_workers": (_i, [_i, _i]),
     "jdet_conv3x3_wgrad_rows": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p]),
     "jdet_conv3x3_dgrad_rows": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p]),
-}
-
-# include/jdet_hip_rows_fwd.h (csrc/conv_rows.hip; same library, a table of its own because tests/test_conv_rows_cpu.py pins
-# the names of ROWS_SIGNATURES; tests/test_conv_rows_fwd_cpu.py checks it against the header and the exports)
-ROWS_FWD_SIGNATURES = {
+    # the row-sparse convolution forward
     "jdet_rows_from_flags_workspace": (_sz, [_i, _i, _i]),
     "jdet_rows_from_flags": (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _p, _sz, _p]),
     "jdet_conv3x3_rows_forward_supported": (_i, [_i, _i]),
     "jdet_conv3x3_rows_forward": (_i, [_p, _p, _p, _i, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p]),
-}
-
-# include/jdet_hip_fcos.h (csrc/fcos_targets.hip, csrc/poly_iou_loss.hip; same library, a table of its own for the reason
-# ATSS_SIGNATURES has one; tests/test_fcos_cpu.py checks it against the header and the exports)
-FCOS_SIGNATURES = {
+    # rotated FCOS
     "jdet_fcos_targets": (_i, [_p, _p, _i, _p, _p, _p, _i, _i, _i, _i, _i, _f, _p, _p, _p, _p, _p]),
     "jdet_poly_iou_loss": (_i, [_p, _p, _p, _l, _i, _f, _p, _p, _p]),
-}
-
-# include/jdet_hip_reppoints.h (csrc/convex_point_assign.hip, csrc/convex_giou_loss.hip; same library, a table of its own
-# for the reason ATSS_SIGNATURES has one; tests/test_reppoints_cpu.py checks it against the header and the exports)
-REPPOINTS_SIGNATURES = {
+    # Rotated RepPoints
     "jdet_convex_point_assign_workspace": (_sz, [_i, _i]),
     "jdet_convex_point_assign": (_i, [_p, _i, _i, _p, _p, _i, _p, _p, _p, _i, _i, _f, _i, _i, _p, _p, _p, _sz, _p]),
     "jdet_convex_giou_loss": (_i, [_p, _p, _p, _p, _l, _p, _p, _p]),
-}
-
-# include/jdet_hip_h2rbox.h (csrc/rotate_crop.hip, csrc/h2rbox_aug_loss.hip; same library, a table of its own for the
-# reason ATSS_SIGNATURES has one; tests/test_h2rbox_cpu.py checks it against the header and the exports)
-H2RBOX_SIGNATURES = {
+    # H2RBox
     "jdet_rotate_crop": (_i, [_p, _i, _i, _i, _i, _i, _i, _f, _f, _i, _p, _p]),
     "jdet_h2rbox_aug_loss_forward": (_i, [_p, _i, _p, _p, _p, _p, _p, _i, _i, _f, _f, _f, _i, _i, _f, _f, _f, _p, _p, _p]),
     "jdet_h2rbox_aug_loss_backward": (_i, [_p, _i, _p, _p, _p, _p, _p, _i, _i, _f, _f, _f, _i, _i, _f, _f, _f, _p, _p, _p,
                                            _p, _p, _p, _p, _p]),
-}
-
-# include/jdet_hip_ld.h (csrc/dist_loss.hip; same library, a table of its own for the reason ATSS_SIGNATURES has one;
-# tests/test_ld_cpu.py checks it against the header and the exports)
-LD_SIGNATURES = {
+    # localization distillation
     "jdet_dist_integral": (_i, [_p, _l, _i, _f, _f, _f, _f, _p, _p]),
     "jdet_dist_bbox_loss_level": (_i, [_p, _p, _l, _l, _p, _l, _l, _l, _i, _f, _f, _f, _f, _f, _p, _f, _p, _p, _p, _sz, _p]),
     "jdet_kd_kl_div_level_forward": (_i, [_p, _p, _p, _l, _l, _l, _i, _f, _f, _p, _p, _p, _sz, _p]),
     "jdet_kd_kl_div_level_backward": (_i, [_p, _p, _p, _l, _l, _l, _i, _f, _f, _p, _p, _p, _p]),
-}
-
-# include/jdet_hip_bf16x3.h (csrc/conv_bf16x3.hip; same library, a table of its own for the reason ROWS_FWD_SIGNATURES has
-# one; tests/test_conv_bf16x3_cpu.py checks it against the header and the exports)
-BF16X3_SIGNATURES = {
+    # the 3x3 convolution forward on bf16 MFMA
     "jdet_conv3x3_bf16x3_supported": (_i, [_i, _i]),
     "jdet_conv3x3_bf16x3_forward": (_i, [_p, _i, _i, _i, _i, _p, _i, _p, _i, _p, _p, _p]),
 }
@@ -245,9 +214,7 @@ def lib():
         # process and our DT_NEEDED entry resolves to that same runtime: one HIP context, shared
         # streams and allocations.
         l = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(ATSS_SIGNATURES.items()) + list(ROWS_SIGNATURES.items()) + \
-                list(ROWS_FWD_SIGNATURES.items()) + list(FCOS_SIGNATURES.items()) + list(REPPOINTS_SIGNATURES.items()) + \
-                list(H2RBOX_SIGNATURES.items()) + list(LD_SIGNATURES.items()) + list(BF16X3_SIGNATURES.items()):
+        for name, (res, args) in SIGNATURES.items():
             fn = getattr(l, name)  # AttributeError here == ABI drift: fail loudly
             fn.restype = res
             fn.argtypes = args

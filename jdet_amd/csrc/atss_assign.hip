@@ -5,7 +5,7 @@
 //                                                   a Python loop over gts, a second (K * A) "-INF" matrix
 //   python/jdet/models/boxes/box_ops.py:L725-741    points_in_rotated_boxes (atan2 / cos / sin per pair)
 // The rules the reference leaves open (tie order, the clamp to the level size, the algebraic inside test) are stated
-// in include/jdet_hip_atss.h.
+// in include/jdet_hip.h.
 //
 // MI355X design (not a translation).  Only K x C pairs (C = sum over levels of min(topk, n_level), 45 at config size)
 // decide anything, so nothing of size (A, K) is computed or stored; the cost is launch latency, three launches:
@@ -20,7 +20,7 @@
 //                         every lane tests threshold + inside and claims its anchor with a 64-bit atomicMax.
 //   3. atss_write_kernel  one lane per anchor unpacks its key into gt_inds / max_overlaps / labels.
 // No host synchronisation, no allocation, fixed shapes: the step captures into a HIP graph.
-#include "jdet_hip_atss.h"
+#include "jdet_hip.h"
 #include "rotated_iou.h"
 
 namespace {

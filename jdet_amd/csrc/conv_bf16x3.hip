@@ -1,5 +1,5 @@
 // 3x3 / stride 1 / pad 1 channels-last forward convolution, fp32 in and out, on the bf16 matrix pipe through an exact
-// three-way split of every fp32 operand (include/jdet_hip_bf16x3.h).  The same implicit GEMM as conv_igemm.hip
+// three-way split of every fp32 operand (include/jdet_hip.h).  The same implicit GEMM as conv_igemm.hip
 //   Y[m, n] = sum_{tap, c} X[pixel(m) + tap, c] * Wt[n, (tap, c)]          m = (image, y, x), n = output channel
 // for the big dense 256 -> 256 layers that sit at the fp32 MFMA's limit there (v_mfma_f32_32x32x2_f32: 64 cycles for 4 096
 // FLOP; v_mfma_f32_32x32x16_bf16: 32 cycles for 32 768).
@@ -32,7 +32,7 @@
 //     step s + 1 scheduled between the MFMAs of step s, one barrier per K step; XCD-aware tile order; the epilogue (+ bias, ReLU,
 //     x row mask) is conv_igemm.hip's, statement for statement.
 #include "conv_mfma.h"
-#include "jdet_hip_bf16x3.h"
+#include "jdet_hip.h"
 
 namespace {
 

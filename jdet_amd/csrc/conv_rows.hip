@@ -18,7 +18,7 @@
 //                            tile taken from the list and an epilogue that scatters rows; Wd = the flipped weights of
 //                            jdet_conv_dgrad_weights
 //
-// and, for the FORWARD of a tower whose output only that loss reads (include/jdet_hip_rows_fwd.h; in training the ODM
+// and, for the FORWARD of a tower whose output only that loss reads (include/jdet_hip.h; in training the ODM
 // regression tower, whose prediction bbox_decode / AlignConv do not read):
 //
 //   jdet_rows_from_flags       a flag byte per position -> the ascending lists of the flagged rows, of their 3x3 dilation
@@ -31,8 +31,7 @@
 // computed correctly, only slower than by the dense kernels.  List entries past a count are -1 and never read.
 // Results equal the dense computation with the exact zeros left out of the sums.
 #include "conv_mfma.h"
-#include "jdet_hip_rows.h"
-#include "jdet_hip_rows_fwd.h"
+#include "jdet_hip.h"
 
 namespace {
 
@@ -591,7 +590,7 @@ JDET_API int jdet_conv3x3_dgrad_rows(const float* gy_nhwc, const float* wd_crsk,
 }
 
 // =====================================================================================================================
-// include/jdet_hip_rows_fwd.h
+// the row-sparse forward
 
 JDET_API size_t jdet_rows_from_flags_workspace(int N, int H, int W) {
   if (N <= 0 || H <= 0 || W <= 0) return 0;

@@ -2,14 +2,14 @@
 //
 // Reference semantics: python/jdet/models/losses/convex_giou_loss.py:L10-53 (ConvexGIoULossFunction.execute) on the
 // rows that python/jdet/models/roi_heads/rotated_reppoints_head.py:L612-634 gathers with nonzero() and divides by
-// normalize_term.  The operations and their order are stated in include/jdet_hip_reppoints.h.
+// normalize_term.  The operations and their order are stated in include/jdet_hip.h.
 //
 // MI355X design.  The head's nonzero() is one host round trip per (level, stage), ten per step; here every row of a
 // stage goes through one launch and a row of weight 0 leaves at once.  Half a wavefront per row, as in
 // csrc/convex_giou.hip: lane j < 18 carries the dual seed of coordinate j, lane 18 the value, all through the shared
 // jdet_convex_giou_dual.  The "any component > 1" rule of a row is one ballot over its half of the wavefront.
 #include "convex_giou.h"
-#include "jdet_hip_reppoints.h"
+#include "jdet_hip.h"
 
 namespace {
 

@@ -5,7 +5,7 @@
 //                                                   tensor, a topk, two scatter writes -- ~8 launches and several
 //                                                   host syncs per gt, for at most pos_num positives per gt
 // The rules (level of a gt, distance, tie order, the clamp to the level size, conflicts) are stated in
-// include/jdet_hip_reppoints.h.
+// include/jdet_hip.h.
 //
 // MI355X design (not a translation).  The work is a few hundred KB of reads; the cost is launches and syncs, so the
 // whole batch is three launches and no sync:
@@ -19,7 +19,7 @@
 //                            (distance bits << 32 | g): order-independent, hence deterministic.
 //   3. convex_write_kernel   one lane per (image, point) unpacks its key into gt_inds / labels.
 #include "common.h"
-#include "jdet_hip_reppoints.h"
+#include "jdet_hip.h"
 
 #include <math.h>
 

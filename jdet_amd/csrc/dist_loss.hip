@@ -1,4 +1,4 @@
-// Localization distillation for RetinaNet-OBB (include/jdet_hip_ld.h): the regression branch predicts, per anchor,
+// Localization distillation for RetinaNet-OBB (include/jdet_hip.h): the regression branch predicts, per anchor,
 // five distributions of reg_max + 1 logits instead of five numbers.
 //
 //   jdet_dist_integral          box_ops.integral / integral_angle: the expectation of each distribution
@@ -14,7 +14,7 @@
 // (dist_softmax.h).  Row arithmetic and sums are double and rounded once: the float64 references of tests/ld_ref.py are
 // then met to the last float, whatever the summation order of the float32 composition happens to be.
 #include "dist_softmax.h"
-#include "jdet_hip_ld.h"
+#include "jdet_hip.h"
 #include "reduce.h"
 
 namespace {

@@ -4,7 +4,7 @@
 //   python/jdet/models/roi_heads/fcos_head.py:L535-670   (points x gts) areas, ranges, offsets, 2x2 matrices, four
 //                                                        distances, two masks, an argmin and two gathers
 //   python/jdet/models/boxes/box_ops.py:L679-692         mintheta_obb
-// The rules (matrix, inside, range, tie, background, empty image) are stated in include/jdet_hip_fcos.h.
+// The rules (matrix, inside, range, tie, background, empty image) are stated in include/jdet_hip.h.
 //
 // MI355X design (not a translation).  Nothing of size (points x gts) exists: one thread owns one (image, point), computes
 // its coordinates from its index and keeps the running winner in registers.  The image's gts are walked in chunks of
@@ -12,7 +12,7 @@
 // label), so the inner loop is LDS broadcasts and a dozen flops.  The gt count is read from the device, so the call
 // needs no host sync; one launch covers all images and levels.  Bandwidth is 8 output words per point: latency-bound.
 #include "common.h"
-#include "jdet_hip_fcos.h"
+#include "jdet_hip.h"
 
 namespace {
 

@@ -6,7 +6,7 @@
 //                                                          .any(), gathers, distance2obb, the rotated targets
 //   python/jdet/models/losses/h2rbox_loss.py:L42-66        centre L1 + min(shape IoU + |sin|, swapped IoU + |cos|)
 //   python/jdet/models/boxes/box_ops.py:L694-707           distance2obb (regular_obb included)
-// The rules (cell map, tie rule, validity, target, terms, gradient conventions) are stated in include/jdet_hip_h2rbox.h.
+// The rules (cell map, tie rule, validity, target, terms, gradient conventions) are stated in include/jdet_hip.h.
 //
 // MI355X design (not a translation).  Dense and fixed-shape: one thread owns one view-1 point of one image, finds its
 // level and cell from its index, and skips everything (both prediction reads included) when its weight is 0 or its
@@ -18,7 +18,7 @@
 // 3 x 3 block its inverse map points at, in ascending index: deterministic, no floating-point atomics.
 // Everything is latency-bound at N ~ 22k points per image; the win is the absence of host syncs and of ~60 launches.
 #include "common.h"
-#include "jdet_hip_h2rbox.h"
+#include "jdet_hip.h"
 
 namespace {
 

@@ -4,7 +4,7 @@
 //   python/jdet/models/losses/poly_iou_loss.py:L11-36    shoelace, convex_areas (convex_sort + gather)
 //   python/jdet/models/losses/poly_iou_loss.py:L39-86    poly_intersection (16 edge pairs, two inside masks)
 //   python/jdet/models/losses/poly_iou_loss.py:L97-123   iou, clamp, -log / 1 - iou, weight
-// The operations, their order and the gradient rules are stated in include/jdet_hip_fcos.h.
+// The operations, their order and the gradient rules are stated in include/jdet_hip.h.
 //
 // MI355X design.  One thread per row; a row is a few hundred flops on 24 points.  The 24 points and masks of a lane live
 // in LDS at [k * 64 + lane] (conflict-free, dynamic indexing without scratch); the scan's sort keys and the hull indices
@@ -15,7 +15,7 @@
 // forward + backward with the decoding ops around it (profiles/fcos.md).
 #include "common.h"
 #include "graham_scan.h"
-#include "jdet_hip_fcos.h"
+#include "jdet_hip.h"
 
 namespace {
 

@@ -4,7 +4,7 @@
 //   python/jdet/models/networks/h2rbox.py:L35-75   linspace x linspace grid (n, h, w, 2), a (n h w, 2) x (2, 2) matmul,
 //                                                  grid_sample(bilinear, padding, align_corners=True) over the whole
 //                                                  frame, then the centre crop
-// The per-pixel rule is stated in include/jdet_hip_h2rbox.h.
+// The per-pixel rule is stated in include/jdet_hip.h.
 //
 // MI355X design (not a translation).  Only the cropped window is computed and the grid never exists: one thread owns one
 // output pixel (n, y, x), derives its source position from its index in double (a dozen operations, shared by all C
@@ -14,7 +14,7 @@
 // call moves 25 MB in and 25 MB out: bandwidth-bound, one launch instead of linspace / meshgrid / stack / matmul /
 // grid_sample / slice and their 16 MB grid.
 #include "common.h"
-#include "jdet_hip_h2rbox.h"
+#include "jdet_hip.h"
 
 namespace {
 

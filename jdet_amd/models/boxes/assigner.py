@@ -149,7 +149,7 @@ class ATSSAssignerRbbox:
     level nearest to its centre are candidates; those whose IoU reaches mean + std of the candidates' IoUs and whose
     centre lies inside the gt are positive; an anchor claimed twice goes to the higher IoU.  0 negative, k > 0 matched
     to gt k - 1 (nothing is ignored).  Tie order, the clamp of topk to a level's size and the form of the inside test
-    are this project's rules: include/jdet_hip_atss.h.
+    are this project's rules: include/jdet_hip.h.
 
     With `BboxOverlaps2D_rotated` as the calculator (the config's) the IoU of the candidate pairs is computed inside
     the kernel, bit-equal to the calculator's matrix; any other calculator is evaluated to its (A, K) matrix and the
@@ -218,7 +218,7 @@ class ConvexAssigner:
     """RepPoints init-stage assignment (assigner.py:L393-548): every gt claims the `pos_num` points nearest to the centre
     of its horizontal box, in the pyramid level its size selects; a point claimed twice goes to the nearer gt.  0
     negative, k > 0 matched to gt k - 1.  The level of a gt, the tie order and the clamp of pos_num to a level's size
-    are stated in include/jdet_hip_reppoints.h."""
+    are stated in include/jdet_hip.h."""
 
     def __init__(self, scale=4, pos_num=3, assigned_labels_filled=0):
         self.scale = scale

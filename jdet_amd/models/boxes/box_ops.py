@@ -109,7 +109,7 @@ def points_in_rotated_boxes(points, rrects):
     """(n, 2+) points x (m, 5) boxes -> (n, m) bool, True where the point lies inside the box.  The tensor program of
     box_ops.py:L725-741 as written (atan2 of the offset, cos / sin of the angle difference), kept for API parity: the
     fused assigner (csrc/atss_assign.hip) tests only its candidates, in the algebraic form stated in
-    include/jdet_hip_atss.h."""
+    include/jdet_hip.h."""
     offsets = points[:, None, :2] - rrects[None, :, :2]
     offset_angles = torch.atan2(offsets[..., 1], offsets[..., 0])
     offset_distances = offsets.square().sum(-1).sqrt()

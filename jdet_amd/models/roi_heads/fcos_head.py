@@ -12,7 +12,7 @@ Both routes return their losses together with the intermediates behind them (`_D
 adds its consistency term to them and overrides only the box-loss hooks.  Padded gts and post-processing are the ones
 every single-stage head shares (_dense_head_common.py).
 Where the reference leaves a rule open or gets it wrong (ties, background targets, images without gts) both routes
-follow include/jdet_hip_fcos.h."""
+follow include/jdet_hip.h."""
 import ctypes
 from collections import namedtuple
 
@@ -252,7 +252,7 @@ class FCOSHead(nn.Module):
 
     def _get_target_single(self, gt_bboxes, gt_labels, points, regress_ranges, num_points_per_lvl):
         """one image, the reference's tensor program (L599-670); background rows are zeroed, an image without gts is
-        background everywhere (include/jdet_hip_fcos.h)"""
+        background everywhere (include/jdet_hip.h)"""
         num_points = points.size(0)
         num_gts = gt_labels.size(0)
         if num_gts == 0:

@@ -19,8 +19,8 @@ Label conventions (the reference's, kept):
   rotation_agnostic_classes  compared with the 1-BASED labels of the positives (the reference adds 1 to the labels
                              before it gathers them, L387/L440): class ids 1 .. num_classes;
   rect_classes               compared with the labels multiclass_nms_rotated returns at inference: 0-BASED.
-Images without gts and background rows follow include/jdet_hip_fcos.h (background everywhere / zero targets); the
-rounding of the cell map is round-half-to-even (include/jdet_hip_h2rbox.h)."""
+Images without gts and background rows follow include/jdet_hip.h (background everywhere / zero targets); the
+rounding of the cell map is round-half-to-even (include/jdet_hip.h)."""
 import math
 
 import torch

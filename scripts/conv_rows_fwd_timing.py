@@ -1,5 +1,5 @@
 """usage (GPU box): python scripts/conv_rows_fwd_timing.py [--iters 20] -- HIP-event times of the entry points of
-include/jdet_hip_rows_fwd.h (jdet_rows_from_flags; jdet_conv3x3_rows_forward incl. its zero fill) at the S2ANet ODM
+include/jdet_hip.h (jdet_rows_from_flags; jdet_conv3x3_rows_forward incl. its zero fill) at the S2ANet ODM
 regression tower's shapes (P3: 2 x 128 x 128, the packed P4..P7 canvas: 2 x 64 x 97; 256 -> 256 channels, bias + ReLU),
 beside the dense forward (csrc/conv_igemm.hip) in the same process on the same device.  Flags: a few seed rows per map
 (the positive anchors of profiles/conv_rows.md) -- the tower's second layer then runs on their first dilation, its

@@ -4,7 +4,12 @@ Importable without a GPU (tests/test_guarded_cpu.py checks that no entry point i
 tests/test_gpu_abi_buffers.py.
 
 Every bound below is the bound of the existing test of that kernel, cited next to it; bit-exact kernels (copies,
-codec-free index work, NMS keep sets) are compared for equality."""
+codec-free index work, NMS keep sets) are compared for equality.
+
+The detector features (ATSS, FCOS, RepPoints, H2RBox, localization distillation) and the row-sparse / bf16x3
+convolutions have factories that return a `Case`: their smallest instances are rows here, and their feature tests
+(tests/test_gpu_<feature>.py) run the same factories over every regime of the kernel.  Every builder reaches the
+library through this module's `lib()`: the CPU dry run replaces it."""
 import ctypes
 import math
 
@@ -1865,3 +1870,667 @@ def _convex_sort(npts, circular):
 for _npts in (9, 64):
     for _circ in (1, 0):
         row("jdet_convex_sort", "nbs 33 npts %d circular %d" % (_npts, _circ))(_convex_sort(_npts, _circ))
+
+
+# ======================================================================================================================
+# the ATSS assigner (tests/test_gpu_atss.py): the restatement of tests/atss_ref.py as the reference, everything exact
+# ======================================================================================================================
+def atss_case(name, matrix):
+    from tests import atss_ref as R
+    anchors, num_level, gts, labels, ref = R.fixture(name)
+    A, K, nl = anchors.shape[0], gts.shape[0], len(num_level)
+    offs = R.level_offsets(num_level)
+    ov0 = R.iou_matrix(anchors, gts) if matrix else None
+
+    def fn(run):
+        a, g, gl = run.inp("anchors", anchors.copy()), run.inp("gt", gts.copy()), run.inp("gt_labels", labels.copy())
+        ov = run.inp("overlaps", ov0) if matrix else None
+        gt_inds, max_ov, lab = run.out("gt_inds", (A,), I32), run.out("max_overlaps", (A,)), run.out("labels", (A,), I32)
+        ws, wsb = run.ws("workspace", lib().jdet_atss_assign_workspace(A, K, nl, R.TOPK))
+        run.ok(lib().jdet_atss_assign(P(a), A, 5, (ctypes.c_int32 * (nl + 1))(*offs.tolist()), nl, P(g), K, P(gl), P(ov),
+                                      R.TOPK, 0, P(gt_inds), P(max_ov), P(lab), P(ws), wsb, ST(a)), "jdet_atss_assign")
+        return Res({"gt_inds": gt_inds, "max_overlaps": max_ov, "labels": lab},
+                   lambda: {"gt_inds": exact(ref["gt_inds"]), "max_overlaps": exact(ref["max_overlaps"]),
+                            "labels": exact(ref["labels"])})
+    return Case(("jdet_atss_assign",), "%s %s dirty workspace" % (name, "matrix" if matrix else "fused"), fn)
+
+
+CASES.append(atss_case("256a", False))
+CASES.append(atss_case("256a", True))
+
+
+# ======================================================================================================================
+# the row-sparse 3x3 convolutions (csrc/conv_rows.hip): lists of 3 % and of all rows, the corners and the image boundary
+# among them; position 0 next to every list
+# ======================================================================================================================
+ROWS_BOUND = (2e-5, 1e-6)     # tests/test_gpu_conv_rows.py, test_gpu_conv_rows_fwd.py (= tests/test_gpu_conv_igemm.py:45, test_gpu_conv_wgrad.py:48)
+ROWS_SHAPES = [(2, 13, 17, 64, 64), (1, 8, 8, 256, 256), (2, 20, 24, 32, 256)]
+ROWS_FRACS = (0.03, 1.0)
+
+
+def dilate3x3(nz):
+    """(N, H, W) bool -> the 3x3 dilation inside each image"""
+    N, H, W = nz.shape
+    pad = np.pad(nz, ((0, 0), (1, 1), (1, 1)))
+    out = np.zeros_like(nz)
+    for dy in range(3):
+        for dx in range(3):
+            out |= pad[:, dy:dy + H, dx:dx + W]
+    return out
+
+
+def _listed_rows(rng, N, H, W, frac):
+    P_ = N * H * W
+    rows = np.sort(rng.choice(P_, max(1, int(round(frac * P_))), replace=False))
+    return np.unique(np.concatenate([rows, [0, W - 1, H * W - 1, P_ - 1]]))       # corners and the image boundary
+
+
+def _padded_list(a, n):
+    out = np.full(n, -1, np.int32)
+    out[:len(a)] = a
+    return out
+
+
+def rows_inputs(shape, frac):
+    """x, w (Cout,Cin,3,3), gy zero outside the listed rows, the list, the list of its dilation"""
+    N, H, W, Cin, Cout = shape
+    P_ = N * H * W
+    rng = np.random.default_rng(N * 1000 + H * 100 + W + Cin + int(frac * 64))
+    x = rng.standard_normal((N, H, W, Cin)).astype(np.float32)
+    w = (rng.standard_normal((Cout, Cin, 3, 3)) * (2.0 / (9 * Cin)) ** 0.5).astype(np.float32)
+    rows = _listed_rows(rng, N, H, W, frac)
+    g = np.zeros((P_, Cout), np.float32)
+    g[rows] = rng.standard_normal((len(rows), Cout)).astype(np.float32)
+    nz = np.zeros(P_, bool)
+    nz[rows] = True
+    dil = dilate3x3(nz.reshape(N, H, W))
+    return x, w, g.reshape(N, H, W, Cout), rows.astype(np.int32), np.flatnonzero(dil.reshape(-1)).astype(np.int32)
+
+
+def _rows_grads64(x, w, g):
+    x64 = torch.from_numpy(x).double().permute(0, 3, 1, 2).requires_grad_(True)
+    w64 = torch.from_numpy(w).double().requires_grad_(True)
+    gx, gw = torch.autograd.grad(F.conv2d(x64, w64, None, 1, 1), (x64, w64), torch.from_numpy(g).double().permute(0, 3, 1, 2))
+    return gx.permute(0, 2, 3, 1).contiguous(), gw.permute(0, 2, 3, 1).contiguous()
+
+
+def rows_case(entry, shape, frac):
+    N, H, W, Cin, Cout = shape
+    P_ = N * H * W
+    x0, w0, g0, rows0, drows0 = rows_inputs(shape, frac)
+
+    def nonzero(run):
+        g = run.inp("g", g0)
+        flags, rows, drows = run.out("flags", (P_,), U8), run.out("rows", (P_,), I32), run.out("rows_dilated", (P_,), I32)
+        counts = run.out("counts", (2,), I32)
+        ws, wsb = run.ws("workspace", lib().jdet_rows_nonzero_workspace(N, H, W))
+        run.ok(lib().jdet_rows_nonzero(P(g), N, H, W, Cout, P(flags), P(rows), P(drows), P(counts), P(ws), wsb, ST(g)),
+               entry)
+        want = np.zeros(P_, np.uint8)
+        want[rows0] = 1
+        return Res({"flags": flags, "rows": rows, "rows_dilated": drows, "counts": counts},
+                   lambda: {"flags": exact(want), "rows": exact(_padded_list(rows0, P_)),
+                            "rows_dilated": exact(_padded_list(drows0, P_)),
+                            "counts": exact(np.asarray([len(rows0), len(drows0)], np.int32))})
+
+    def wgrad(run):
+        x, g = run.inp("x", x0), run.inp("gy", g0)
+        rows, count = run.inp("rows", rows0), run.inp("count", np.asarray([len(rows0)], np.int32))     # no entry past the count
+        base = np.random.default_rng(5).standard_normal((Cout, 3, 3, Cin)).astype(np.float32)
+        gw = run.acc("gw", base)
+        run.ok(lib().jdet_conv3x3_wgrad_rows(P(x), P(g), P(rows), P(count), N, H, W, Cin, Cout, P(gw), ST(x)), entry)
+
+        def ref():
+            # the value is out - base in float64, so the fp32 roundings of adding onto the base count as error: at most
+            # jdet_conv3x3_wgrad_rows_workers() workgroups add to an element, each addition rounds by at most 2^-24 of the
+            # running value
+            r, bound = rel(_rows_grads64(x0, w0, g0)[1], *ROWS_BOUND)
+            return {"gw": (r, bound + lib().jdet_conv3x3_wgrad_rows_workers(Cin, Cout) * 2.0 ** -24 * float(np.abs(base).max() + np.abs(r).max()))}
+        return Res({"gw": gw}, ref, atomic=True)
+
+    def dgrad(run):
+        g = run.inp("gy", g0)
+        wd = run.inp("wd", np.ascontiguousarray(w0[:, :, ::-1, ::-1].transpose(1, 2, 3, 0)))
+        rows, count = run.inp("rows", drows0), run.inp("count", np.asarray([len(drows0)], np.int32))
+        gx = run.out("gx", (N, H, W, Cin))
+        run.ok(lib().jdet_conv3x3_dgrad_rows(P(g), P(wd), P(rows), P(count), N, H, W, Cin, Cout, 1, P(gx), ST(g)), entry)
+        return Res({"gx": gx}, lambda: {"gx": rel(_rows_grads64(x0, w0, g0)[0], *ROWS_BOUND)})
+
+    fn = {"jdet_rows_nonzero": nonzero, "jdet_conv3x3_wgrad_rows": wgrad, "jdet_conv3x3_dgrad_rows": dgrad}[entry]
+    return Case((entry,), "x(%d,%d,%d,%d) Cout %d rows %.0f%%" % (N, H, W, Cin, Cout, 100 * frac), fn)
+
+
+def rows_fwd_inputs(shape, frac):
+    N, H, W, Cin, Cout = shape
+    P_ = N * H * W
+    rng = np.random.default_rng(N * 1000 + H * 100 + W + Cin + int(frac * 64) + 1)
+    x = rng.standard_normal((N, H, W, Cin)).astype(np.float32)
+    w = (rng.standard_normal((Cout, Cin, 3, 3)) * (2.0 / (9 * Cin)) ** 0.5).astype(np.float32)
+    b = (0.3 * rng.standard_normal(Cout)).astype(np.float32)
+    rows = _listed_rows(rng, N, H, W, frac)
+    mask = (rng.random(P_) > 0.2).astype(np.float32)
+    return x, w, b, rows.astype(np.int32), mask
+
+
+def rows_fwd_case(entry, shape, frac):
+    N, H, W, Cin, Cout = shape
+    P_ = N * H * W
+    x0, w0, b0, rows0, mask0 = rows_fwd_inputs(shape, frac)
+
+    def from_flags(run):
+        f0 = np.zeros(P_, np.uint8)
+        f0[rows0] = 1 + (rows0 % 200).astype(np.uint8)          # any non-zero byte is a flag
+        flags = run.inp("flags", f0)
+        outs = [run.out(n, (P_,), I32) for n in ("rows", "rows_dilated", "rows_dilated2")]
+        counts = run.out("counts", (3,), I32)
+        ws, wsb = run.ws("workspace", lib().jdet_rows_from_flags_workspace(N, H, W))
+        run.ok(lib().jdet_rows_from_flags(P(flags), N, H, W, P(outs[0]), P(outs[1]), P(outs[2]), P(counts), P(ws), wsb,
+                                          ST(flags)), entry)
+        nz = (f0 != 0).reshape(N, H, W)
+        want = [np.flatnonzero(nz), np.flatnonzero(dilate3x3(nz)), np.flatnonzero(dilate3x3(dilate3x3(nz)))]
+        return Res({"rows": outs[0], "rows_dilated": outs[1], "rows_dilated2": outs[2], "counts": counts},
+                   lambda: {"rows": exact(_padded_list(want[0], P_)), "rows_dilated": exact(_padded_list(want[1], P_)),
+                            "rows_dilated2": exact(_padded_list(want[2], P_)),
+                            "counts": exact(np.asarray([len(v) for v in want], np.int32))})
+
+    def forward(run):
+        x = run.inp("x", x0)
+        w = run.inp("w", np.ascontiguousarray(w0.transpose(0, 2, 3, 1)))
+        b, mask = run.inp("bias", b0), run.inp("rowmask", mask0)
+        rows, count = run.inp("rows", rows0), run.inp("count", np.asarray([len(rows0)], np.int32))   # no entry past the count
+        y = run.out("y", (N, H, W, Cout))
+        run.ok(lib().jdet_conv3x3_rows_forward(P(x), P(w), P(b), 1, P(mask), P(rows), P(count), N, H, W, Cin, Cout, 1,
+                                               P(y), ST(x)), entry)
+
+        def ref():
+            pre = F.conv2d(torch.from_numpy(x0).double().permute(0, 3, 1, 2), torch.from_numpy(w0).double(),
+                           torch.from_numpy(b0).double(), 1, 1).permute(0, 2, 3, 1).reshape(P_, Cout).numpy()
+            keep = np.zeros(P_)
+            keep[rows0] = mask0[rows0]
+            full = np.maximum(pre, 0.0)
+            r, bound = rel(full, *ROWS_BOUND)          # the bound of the whole map's scale; unlisted / masked rows are 0
+            return {"y": ((full * keep[:, None]).reshape(N, H, W, Cout), bound)}
+        return Res({"y": y}, ref)
+
+    fn = {"jdet_rows_from_flags": from_flags, "jdet_conv3x3_rows_forward": forward}[entry]
+    return Case((entry,), "x(%d,%d,%d,%d) Cout %d rows %.0f%%" % (N, H, W, Cin, Cout, 100 * frac), fn)
+
+
+for _make, _entries in ((rows_case, ("jdet_rows_nonzero", "jdet_conv3x3_wgrad_rows", "jdet_conv3x3_dgrad_rows")),
+                        (rows_fwd_case, ("jdet_rows_from_flags", "jdet_conv3x3_rows_forward"))):
+    for _entry in _entries:
+        for _shape in ROWS_SHAPES:
+            for _frac in ROWS_FRACS:
+                CASES.append(_make(_entry, _shape, _frac))
+
+
+# ======================================================================================================================
+# the 3x3 convolution on bf16 MFMA through the three-way split (tests/test_gpu_conv_bf16x3.py, tests/bf16x3_cases.py)
+# ======================================================================================================================
+def bf16x3_case(case):
+    from tests import bf16x3_cases as BC
+    N, H, W, Cin, Cout = BC.CASES[case]
+    x0, w0, b0, mask0 = BC.inputs(case)
+
+    def fn(run):
+        x, w = run.inp("x", np.array(x0)), run.inp("w", np.array(w0))
+        b, mask = run.inp("bias", np.array(b0)), run.inp("rowmask", np.array(mask0))
+        y = run.out("y", (N, H, W, Cout))
+        run.ok(lib().jdet_conv3x3_bf16x3_forward(P(x), N, H, W, Cin, P(w), Cout, P(b), 1, P(mask), P(y), ST(x)),
+               "jdet_conv3x3_bf16x3_forward")
+
+        def ref():
+            full = np.maximum(BC.reference(case, True), 0.0)
+            bound = BC.BOUND[0] * np.abs(full).max() + BC.BOUND[1]
+            return {"y": (full * mask0.astype(np.float64).reshape(N, H, W, 1), bound)}
+        return Res({"y": y}, ref)
+    return Case(("jdet_conv3x3_bf16x3_forward",), "case " + case, fn)
+
+
+CASES.append(bf16x3_case("b"))
+
+
+# ======================================================================================================================
+# rotated FCOS (tests/test_gpu_fcos.py states the bounds): point targets against the restatement of tests/fcos_ref.py,
+# the polygon IoU loss at 4 x the float32 restatement's own error
+# ======================================================================================================================
+def fcos_ulp(x):
+    return float(np.spacing(np.float32(abs(x))))
+
+
+def fcos_padded(gts, labels, dev, poison=True):
+    """(B, Kmax, 5), (B, Kmax) int32, (B,) int32 on the device; the rows beyond an image's count hold NaN / a wild label"""
+    B, Kmax = len(gts), max(max(len(g) for g in gts), 1)
+    g = np.full((B, Kmax, 5), np.nan if poison else 0.0, np.float32)
+    lab = np.full((B, Kmax), 77 if poison else 0, np.int32)
+    for b in range(B):
+        g[b, :len(gts[b])] = gts[b]
+        lab[b, :len(gts[b])] = labels[b]
+    cnt = np.asarray([len(x) for x in gts], np.int32)
+    return torch.from_numpy(g).to(dev), torch.from_numpy(lab).to(dev), torch.from_numpy(cnt).to(dev)
+
+
+def fcos_centerness_bound(ref, tol, norm_on_bbox):
+    """c = sqrt(m1/M1 * m2/M2) with every distance off by at most d: |dc| <= c * d * (1/m1 + 1/m2) to first order (doubled
+    here), + 4 ulp for the closed form itself; d = tol, divided by the stride where the targets are"""
+    from tests import fcos_ref as R
+    t = ref["bbox_targets"]
+    d = tol / (np.asarray(R.STRIDES, np.float64)[R.points_of()[1]] if norm_on_bbox else 1.0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        b = 2 * ref["centerness"] * d * (1 / np.minimum(t[:, 0], t[:, 2]) + 1 / np.minimum(t[:, 1], t[:, 3]))
+    return np.where(ref["inds"] >= 0, b + 4 * fcos_ulp(1.0), 0.0)
+
+
+def fcos_targets_case(name, norm_on_bbox, center_sampling):
+    from tests import fcos_ref as R
+    gts, labels = R.target_fixture(name)
+    B, N = len(gts), 341
+    refs = [R.targets(g, gl, norm_on_bbox, center_sampling) for g, gl in zip(gts, labels)]
+    tol = 8 * fcos_ulp(max([float(R.IMG)] + [float(np.abs(g[:, :4]).max()) for g in gts if len(g)]))
+    lv = (ctypes.c_int32 * 15)(*[int(v) for (h, w), s in zip(R.SIZES, R.STRIDES) for v in (h, w, s)])
+    rr = (ctypes.c_float * 10)(*[float(v) for r in R.RANGES for v in r])
+
+    def fn(run):
+        g0, l0, c0 = fcos_padded(gts, labels, "cpu", poison=run.hostile)
+        g, gl, gc = run.inp("gt", g0.numpy()), run.inp("gt_labels", l0.numpy(), guard=99), run.inp("gt_count", c0.numpy(),
+                                                                                                   guard=100)
+        lab, tgt = run.out("labels", (B, N), I32), run.out("bbox_targets", (B, N, 5))
+        ctr, inds = run.out("centerness", (B, N)), run.out("gt_inds", (B, N), I32)
+        run.ok(lib().jdet_fcos_targets(lv, rr, 5, P(g), P(gl), P(gc), B, g0.shape[1], R.NUM_CLASSES, int(norm_on_bbox),
+                                       int(center_sampling), R.RADIUS, P(lab), P(tgt), P(ctr), P(inds), ST(g)),
+               "jdet_fcos_targets")
+        return Res({"labels": lab, "bbox_targets": tgt, "centerness": ctr, "gt_inds": inds},
+                   lambda: {"labels": exact(np.stack([r["labels"] for r in refs])),
+                            "gt_inds": exact(np.stack([r["inds"] for r in refs])),
+                            "bbox_targets": (np.stack([r["bbox_targets"] for r in refs]), tol),
+                            "centerness": (np.stack([r["centerness"] for r in refs]),
+                                           np.stack([fcos_centerness_bound(r, tol, norm_on_bbox) for r in refs]))})
+    return Case(("jdet_fcos_targets",), "%s norm %d cs %d" % (name, norm_on_bbox, center_sampling), fn)
+
+
+def fcos_loss_case(weighted):
+    from tests import fcos_ref as R
+    prd, tgt, _ = R.loss_fixture()
+    ref, e_loss, e_grad = R.loss_reference(False, weighted)
+    n = len(prd)
+
+    def fn(run):
+        p, t = run.inp("pred", np.array(prd)), run.inp("target", np.array(tgt))
+        w = run.inp("weight", np.array(R.loss_weights())) if weighted else None
+        loss, grad = run.out("loss", (n,)), run.out("grad_pred", (n, 5))
+        run.ok(lib().jdet_poly_iou_loss(P(p), P(t), P(w), n, 0, 1e-6, P(loss), P(grad), ST(p)), "jdet_poly_iou_loss")
+        gmax = np.abs(ref["grad"]).max(1, keepdims=True)
+        return Res({"loss": loss, "grad_pred": grad},
+                   lambda: {"loss": (ref["loss"], 4 * e_loss),
+                            "grad_pred": (ref["grad"], np.broadcast_to(4 * e_grad * gmax, ref["grad"].shape).copy())})
+    return Case(("jdet_poly_iou_loss",), "257 rows%s" % (" weighted" if weighted else ""), fn)
+
+
+FCOS_CONTRACTS = {
+    "targets k7_k0": lambda: fcos_targets_case("k7_k0", True, False),
+    "targets k7_k0 cs": lambda: fcos_targets_case("k7_k0", True, True),
+    "targets k70 cs": lambda: fcos_targets_case("k70", False, True),
+    "loss": lambda: fcos_loss_case(False),
+    "loss weighted": lambda: fcos_loss_case(True),
+}
+for _k in sorted(FCOS_CONTRACTS):
+    CASES.append(FCOS_CONTRACTS[_k]())
+
+
+# ======================================================================================================================
+# Rotated RepPoints (tests/test_gpu_reppoints.py): the assigner against the sequential loop of tests/reppoints_ref.py,
+# the dense GIoU loss against the general route on the device, both bit for bit
+# ======================================================================================================================
+def giou_loss_rows(seed=5, P=300, n_pos=100):
+    """pred (P, 18), target (P, 8), weight (P), norm (P): n_pos positive rows at random positions (a rotated box and
+    nine points scattered over it), the rest weight 0 with NaN in pred and target; norm per row in {16, 32, 64}"""
+    from tests import reppoints_ref as R
+    rng = np.random.default_rng(seed)
+    pos = np.sort(rng.choice(P, n_pos, replace=False))
+    norm = rng.choice(np.asarray([16.0, 32.0, 64.0], np.float32), P).astype(np.float32)
+    pred = np.full((P, 18), np.nan, np.float32)
+    target = np.full((P, 8), np.nan, np.float32)
+    weight = np.zeros(P, np.float32)
+    c = rng.uniform(50, 200, (n_pos, 2))
+    wh = np.exp(rng.uniform(np.log(16.0), np.log(160.0), (n_pos, 2)))
+    target[pos] = R.obb_poly(c, wh, rng.uniform(-np.pi / 2, np.pi / 2, n_pos))
+    spread = rng.uniform(0.15, 0.8, (n_pos, 1, 1)) * wh.mean(1)[:, None, None]
+    shift = rng.uniform(-0.5, 0.5, (n_pos, 1, 2)) * wh[:, None, :]
+    pred[pos] = (c[:, None, :] + shift + rng.normal(0, 1, (n_pos, 9, 2)) * spread).reshape(n_pos, 18).astype(np.float32)
+    weight[pos] = rng.uniform(0.5, 2.0, n_pos).astype(np.float32)
+    return pred, target, weight, norm, pos
+
+
+def giou_general_rows(pred, target, weight, norm):
+    """the general route on device tensors of the positive rows: torch fp32 division, reppoints_convex_giou, the rule"""
+    from jdet_amd.models.losses.convex_giou_loss import convex_giou_rows
+    loss, grad = convex_giou_rows(pred / norm[:, None], target / norm[:, None], weight)
+    return loss, grad / norm[:, None]
+
+
+def point_assign_case(name, pos_num, with_labels, stride):
+    from tests import reppoints_ref as R
+    fx = R.fixture(name)
+    B, Kmax, N = fx["gt"].shape[0], fx["gt"].shape[1], len(fx["points"])
+    refs = [R.assign_loop(fx["points"], fx["sizes"], fx["level_ids"], fx["gt"][b, :k], fx["labels"][b, :k],
+                          pos_num=pos_num, labels_filled=-1) for b, k in enumerate(fx["counts"])]
+    offs = (ctypes.c_int32 * 6)(*np.concatenate([[0], np.cumsum(fx["sizes"])]).tolist())
+    ids = (ctypes.c_int32 * 5)(*fx["level_ids"])
+
+    def fn(run):
+        gt = fx["gt"].copy()
+        if run.hostile:                                     # rows beyond an image's count are never read
+            for b, k in enumerate(fx["counts"]):
+                gt[b, k:] = np.nan
+        pts = run.strided("points", fx["points"], stride)
+        g, gl = run.inp("gt", gt), run.inp("gt_labels", fx["labels"], guard=99)
+        gc = run.inp("gt_count", np.asarray(fx["counts"], np.int32), guard=100)
+        gi = run.out("gt_inds", (B, N), I32)
+        lab = run.out("labels", (B, N), I32) if with_labels else None
+        ws, wsb = run.ws("workspace", lib().jdet_convex_point_assign_workspace(B, N))
+        run.ok(lib().jdet_convex_point_assign(P(pts), N, stride, offs, ids, 5, P(g), P(gl) if with_labels else None,
+                                              P(gc), B, Kmax, R.SCALE, pos_num, -1, P(gi), P(lab), P(ws), wsb, ST(g)),
+               "jdet_convex_point_assign")
+        outs = {"gt_inds": gi}
+        want = {"gt_inds": exact(np.stack([r["gt_inds"] for r in refs]))}
+        if with_labels:
+            outs["labels"] = lab
+            want["labels"] = exact(np.stack([r["labels"] for r in refs]))
+        return Res(outs, lambda: want)
+    return Case(("jdet_convex_point_assign",), "%s pos_num %d%s stride %d" % (name, pos_num,
+                                                                               " labels" if with_labels else "", stride), fn)
+
+
+def giou_loss_case():
+    pred, target, weight, norm, pos = giou_loss_rows(seed=7, P=131, n_pos=40)
+
+    def fn(run):
+        nm = norm.copy()
+        if run.hostile:                                     # a row of weight 0 does not read its norm either
+            nm[weight == 0] = np.nan
+        p, tg, w, n = run.inp("pred", pred), run.inp("target", target), run.inp("weight", weight), run.inp("norm", nm)
+        loss, grad = run.out("loss", (131,)), run.out("grad_pred", (131, 18))
+        run.ok(lib().jdet_convex_giou_loss(P(p), P(tg), P(w), P(n), 131, P(loss), P(grad), ST(p)),
+               "jdet_convex_giou_loss")
+
+        def ref():
+            want_loss, want_grad = np.zeros(131, np.float32), np.zeros((131, 18), np.float32)
+            # the reference of the positive rows is the general route, which is device code: a run on host buffers
+            # (tests/test_guarded_cpu.py) has the zero rows and the shapes only
+            if run.dev.type == "cuda":
+                t = lambda a: torch.from_numpy(a).to(run.dev)  # noqa: E731
+                ref_loss, ref_grad = giou_general_rows(t(pred[pos]), t(target[pos]), t(weight[pos]), t(norm[pos]))
+                want_loss[pos], want_grad[pos] = ref_loss.cpu().numpy(), ref_grad.cpu().numpy()
+            return {"loss": exact(want_loss), "grad_pred": exact(want_grad)}
+        return Res({"loss": loss, "grad_pred": grad}, ref)
+    return Case(("jdet_convex_giou_loss",), "131 rows, 40 positive", fn)
+
+
+REPPOINTS_CONTRACTS = {
+    "assign b2_256": lambda: point_assign_case("b2_256", 3, True, 4),
+    "assign k70_k0": lambda: point_assign_case("k70_k0", 1, False, 2),
+    "loss": giou_loss_case,
+}
+for _k in sorted(REPPOINTS_CONTRACTS):
+    CASES.append(REPPOINTS_CONTRACTS[_k]())
+
+
+# ======================================================================================================================
+# H2RBox (tests/test_gpu_h2rbox.py states the bounds): every bound is 4 x the error of the float32 restatement of
+# tests/h2rbox_ref.py against the float64 one
+# ======================================================================================================================
+# the issue's two frames, and the non-square one again with a margin of 1 px: there every padding rule acts where H != W
+H2RBOX_FRAMES = {"37x37->32x32": ((37, 37), (32, 32)), "40x56->24x40": ((40, 56), (24, 40)),
+                 "40x56->38x54": ((40, 56), (38, 54))}
+
+
+def rotate_crop_case(frame, theta, padding):
+    from tests import h2rbox_ref as R
+    from jdet_amd.ops.rotate_crop import PADDING
+    (h, w), size = H2RBOX_FRAMES[frame]
+    img = R.image_fixture(h, w)
+
+    def fn(run):
+        x = run.inp("img", img.copy())
+        out = run.out("out", (2, 3) + size)
+        cs, sn = (1.0, 0.0) if theta == 0 else (math.cos(theta), math.sin(theta))
+        run.ok(lib().jdet_rotate_crop(P(x), 2, 3, h, w, size[0], size[1], cs, sn, PADDING[padding], P(out), ST(x)),
+               "jdet_rotate_crop")
+        if theta == 0:
+            ch, cw = (h - size[0]) // 2, (w - size[1]) // 2
+            return Res({"out": out}, lambda: {"out": exact(img[..., ch:ch + size[0], cw:cw + size[1]])})
+        ref, e32 = R.rotate_crop_reference(h, w, size, theta, padding)
+        return Res({"out": out}, lambda: {"out": (ref, 4 * e32)})
+    return Case(("jdet_rotate_crop",), "%s theta %.1f %s" % (frame, theta, padding), fn)
+
+
+def _aug_args(run, rot, win, hostile_rows):
+    from tests import h2rbox_ref as R
+    pred, pred_aug, weight, labels, _ = R.loss_fixture(rot, win)
+    ref = R.loss_reference(rot, win)[0]
+    p1, p2 = pred.copy(), pred_aug.copy()
+    if hostile_rows and run.hostile:                         # the rows nobody may read hold NaN in the hostile runs
+        hit = np.zeros((R.B, R.N), bool)
+        for b in range(R.B):
+            hit[b, ref["aug_index"][b][ref["aug_index"][b] >= 0]] = True
+        p1[weight == 0] = np.nan
+        p2[~hit] = np.nan
+    lv = (ctypes.c_int32 * (3 * len(R.SIZES)))(*[int(v) for (h, w), s in zip(R.SIZES, R.STRIDES) for v in (h, w, s)])
+    ag = (ctypes.c_int32 * len(R.AGNOSTIC))(*R.AGNOSTIC)
+    t = [run.inp("pred", p1), run.inp("pred_aug", p2), run.inp("weight", weight.copy()),
+         run.inp("labels", labels.copy(), guard=99)]
+    rf = R.f32(rot)
+    head = (lv, len(R.SIZES), P(t[0]), P(t[1]), P(t[2]), P(t[3]), ag, len(R.AGNOSTIC), R.B, rf, math.cos(rf), math.sin(rf),
+            R.CROP[0], R.CROP[1], R.WEIGHTS["shape"], R.WEIGHTS["angle"], R.EPS)
+    return head, t, ref, (pred, pred_aug, weight, labels)
+
+
+def _terms64(ref, data, rot):
+    """the error measure of `terms` for the contract rows: exact zeros in the rows that take no part, the weight in
+    column 3 and finite, non-negative terms in the valid rows (the VALUES are held to the float64 column sums in
+    test_aug_terms_select_the_scalar_minimum and, through the loss, in the float64 comparison of
+    tests/test_gpu_h2rbox.py; the contract row adds the guard bands, the full overwrite and B == A bit for bit with NaN
+    in the rows nobody may read)"""
+    from tests import h2rbox_ref as R
+    pred, pred_aug, weight, labels = data
+    valid = ref["aug_index"] >= 0
+
+    def err(v):
+        v = v.reshape(R.B, R.N, 4)
+        bad = np.zeros_like(v)
+        bad[~valid] = np.abs(v[~valid])                      # must be 0
+        bad[valid, 3] = np.abs(v[valid, 3] - weight[valid])  # must be the weight
+        bad[valid, :3] = np.where(np.isfinite(v[valid, :3]) & (v[valid, :3] >= 0), 0.0, 1.0)
+        return bad
+    return err
+
+
+def aug_forward_case(rot, win):
+    from tests import h2rbox_ref as R
+
+    def fn(run):
+        head, t, ref, data = _aug_args(run, rot, win, True)
+        terms, idx = run.out("terms", (R.B, R.N, 4)), run.out("aug_index", (R.B, R.N), I32)
+        run.ok(lib().jdet_h2rbox_aug_loss_forward(*head, P(terms), P(idx), ST(t[0])), "jdet_h2rbox_aug_loss_forward")
+        return Res({"terms": terms, "aug_index": idx},
+                   lambda: {"aug_index": exact(ref["aug_index"]), "terms": (_terms64(ref, data, rot), 0.0)})
+    return Case(("jdet_h2rbox_aug_loss_forward",), "rot %.1f branch %d" % (rot, win), fn)
+
+
+def aug_backward_case(rot, win):
+    from tests import h2rbox_ref as R
+
+    def fn(run):
+        head, t, ref, data = _aug_args(run, rot, win, True)
+        _, e_loss, e_g1, e_g2 = R.loss_reference(rot, win)
+        scale = R.WEIGHTS["loss_weight"] / ref["avg"]
+        idx = run.inp("aug_index", ref["aug_index"].copy(), guard=100)
+        br = run.inp("branch", np.array([win - 1], np.int32), guard=101)
+        sc = run.inp("scale_centre", np.array([scale * R.WEIGHTS["centre"]], np.float32))
+        sb = run.inp("scale_branch", np.array([scale], np.float32))
+        g1, g2 = run.out("grad_pred", (R.B, R.N, 5)), run.out("grad_pred_aug", (R.B, R.N, 5))
+        scratch = run.out("contrib", (R.B, R.N, 5))
+        run.ok(lib().jdet_h2rbox_aug_loss_backward(*head, P(idx), P(br), P(sc), P(sb), P(g1), P(g2), P(scratch),
+                                                   ST(t[0])), "jdet_h2rbox_aug_loss_backward")
+        # the scales enter as float32: one more rounding each (2^-24 relative) on top of the gradient bound
+        m1, m2 = np.abs(ref["grad_pred"]).max(), np.abs(ref["grad_aug"]).max()
+        return Res({"grad_pred": g1, "grad_pred_aug": g2},
+                   lambda: {"grad_pred": (ref["grad_pred"], (4 * e_g1 + 2.0 ** -23) * m1),
+                            "grad_pred_aug": (ref["grad_aug"], (4 * e_g2 + 2.0 ** -23) * m2)})
+    return Case(("jdet_h2rbox_aug_loss_backward",), "rot %.1f branch %d" % (rot, win), fn)
+
+
+H2RBOX_CONTRACTS = {
+    "rotate 37 reflection": lambda: rotate_crop_case("37x37->32x32", -2.5, "reflection"),
+    "rotate 40x56 zeros": lambda: rotate_crop_case("40x56->24x40", 0.3, "zeros"),
+    "rotate 40x56 copy": lambda: rotate_crop_case("40x56->24x40", 0.0, "border"),
+    "rotate 40x56 thin border": lambda: rotate_crop_case("40x56->38x54", -2.5, "border"),
+    "forward branch 1": lambda: aug_forward_case(0.3, 1),
+    "forward branch 2": lambda: aug_forward_case(-2.5, 2),
+    "backward branch 1": lambda: aug_backward_case(0.3, 1),
+    "backward branch 2": lambda: aug_backward_case(math.pi / 2, 2),
+}
+for _k in sorted(H2RBOX_CONTRACTS):
+    CASES.append(H2RBOX_CONTRACTS[_k]())
+
+
+# ======================================================================================================================
+# localization distillation (tests/test_gpu_ld.py states the bounds and the regimes): every bound is 4 x the error of the
+# float32 restatement of tests/ld_ref.py against the float64 one
+# ======================================================================================================================
+def dist_integral_case(rows, reg_max):
+    from tests import ld_ref as R
+    x0 = R.bbox_fixture(rows, reg_max, 0.0, "ones")["logits"]
+    ref = R.integral(x0, reg_max).numpy()
+    e32 = float(np.abs(R.integral(x0, reg_max, torch.float32).double().numpy() - ref).max())
+
+    def fn(run):
+        x, out = run.inp("logits", x0), run.out("deltas", (rows, 5))
+        run.ok(lib().jdet_dist_integral(P(x), rows, reg_max, *R.ENDS, *R.ANGLE_ENDS, P(out), ST(x)), "jdet_dist_integral")
+        assert e32 > 0
+        return Res({"deltas": out}, lambda: {"deltas": (ref, 4 * e32)})          # tests/test_gpu_ld.py: test_integral_against_float64
+    return Case(("jdet_dist_integral",), "rows %d R %d" % (rows, reg_max), fn)
+
+
+def dist_bbox_case(rows, reg_max, beta, wmode, windowed=False, unaligned=False):
+    """contract row of jdet_dist_bbox_loss_level.  windowed: rows = 2 n, target / weight the windows [:, 7:7 + n] of
+    (2, n + 69, 5) arrays whose other rows are NaN; unaligned: logits and gradient 4 bytes off a 16-byte boundary.
+    Hostile runs: NaN in the logits of rows whose five weights are 0 and in the targets of weight 0."""
+    from tests import ld_ref as R
+    f = R.bbox_fixture(rows, reg_max, beta, "ones" if wmode == "zeros" else wmode)
+    weight = np.zeros_like(f["weight"]) if wmode == "zeros" else f["weight"]
+    K5 = 5 * (reg_max + 1)
+
+    def fn(run):
+        x, t = f["logits"].copy(), f["target"].copy()
+        if run.hostile:
+            x[(weight == 0).all(axis=1)] = np.nan
+            t[weight == 0] = np.nan
+        n, total, start = rows, rows, 0
+        tw = [t, weight]
+        if windowed:
+            n = rows // 2
+            total, start = n + 69, 7
+            tw = [R.window(a.reshape(2, n, 5), total, start) for a in tw]
+        pad = 1 if unaligned else 0
+        xin = run.inp("logits", np.concatenate([np.zeros(pad, np.float32), x.reshape(-1)]))
+        tin, win = run.inp("target", tw[0]), run.inp("weight", tw[1])
+        avg = run.inp("avg_factor", np.array([R.AVG], np.float32))
+        loss, grad = run.out("loss", (1,)), run.out("grad_logits", (rows * K5 + pad,))
+        ws, wsb = run.ws("workspace", lib().jdet_sigmoid_focal_loss_workspace())
+        off = start * 5 * 4
+        run.ok(lib().jdet_dist_bbox_loss_level(
+            P(xin) + 4 * pad, P(tin) + off, n, total, P(win) + off, n, total, rows, reg_max, *R.ENDS, *R.ANGLE_ENDS,
+            float(beta), P(avg), R.LOSS_WEIGHT, P(loss), P(grad) + 4 * pad, P(ws), wsb, ST(xin)),
+            "jdet_dist_bbox_loss_level")
+        if pad:                                              # the word in front of the unaligned gradient is nobody's
+            grad[:1].zero_()
+        if wmode == "zeros":
+            return Res({"loss": loss, "grad_logits": grad},
+                       lambda: {"loss": exact(np.zeros(1)), "grad_logits": exact(np.zeros(rows * K5 + pad))})
+        unit = np.concatenate([np.zeros(pad), f["ref"][1].reshape(-1) * (R.AVG / R.LOSS_WEIGHT)])
+        print("bbox rows %d reg_max %d beta %.3f %s: bounds loss %.3e grad %.3e" % (rows, reg_max, beta, wmode, 4 * f["e_loss"], 4 * f["e_grad"]))
+        assert f["e_loss"] > 0 and f["e_grad"] > 0
+        return Res({"loss": loss, "grad_logits": grad},
+                   lambda: {"loss": (np.array([f["ref"][0]]), 4 * f["e_loss"]),
+                            "grad_logits": (unit, 4 * f["e_grad"] * np.abs(unit).max())})
+    return Case(("jdet_dist_bbox_loss_level",), "rows %d R %d beta %.2f %s%s%s" % (
+        rows, reg_max, beta, wmode, " window" if windowed else "", " unaligned" if unaligned else ""), fn)
+
+
+def _kl_blocks(M):
+    return 5 if M % 5 == 0 and M > 5 else (4 if M % 4 == 0 and M > 4 else 1)
+
+
+def _kl_args(run, f, M, K, windowed, unaligned=False):
+    """inputs of both KL entry points -> (pred, soft, weight pointer, rows_per_block, block_stride, tensors)"""
+    from tests import ld_ref as R
+    pred, soft, weight = f["pred"].copy(), f["soft"].copy(), f["weight"]
+    if run.hostile and weight is not None and (weight > 0).any():
+        pred[weight <= 0] = np.nan                           # rows nobody may use
+        soft[weight <= 0] = np.nan
+    pad = 1 if unaligned else 0
+    p = run.inp("pred", np.concatenate([np.zeros(pad, np.float32), pred.reshape(-1)]))
+    s = run.inp("soft", np.concatenate([np.zeros(pad, np.float32), soft.reshape(-1)]))
+    if weight is None:
+        return (P(p) + 4 * pad, P(s) + 4 * pad, None, 1, 0), p
+    if windowed:
+        B = _kl_blocks(M)
+        n = M // B
+        w = run.inp("weight", R.window(weight.reshape(B, n), n + 13, 3))
+        return (P(p) + 4 * pad, P(s) + 4 * pad, P(w) + 3 * 4, n, n + 13), p
+    w = run.inp("weight", weight)
+    return (P(p) + 4 * pad, P(s) + 4 * pad, P(w), M, M), p
+
+
+def kl_forward_case(M, K, T, wmode, windowed=False, unaligned=False):
+    from tests import ld_ref as R
+    f = R.kl_fixture(M, K, T, wmode)
+
+    def fn(run):
+        head, p = _kl_args(run, f, M, K, windowed, unaligned)
+        loss, count = run.out("loss", (1,)), run.out("count", (1,), I32)
+        ws, wsb = run.ws("workspace", lib().jdet_sigmoid_focal_loss_workspace())
+        run.ok(lib().jdet_kd_kl_div_level_forward(*head, M, K, float(T), R.LOSS_WEIGHT, P(loss), P(count), P(ws), wsb,
+                                                  ST(p)), "jdet_kd_kl_div_level_forward")
+        print("kl forward M %d K %d T %d %s: bound %.3e" % (M, K, T, wmode, 4 * f["e_loss"]))
+        assert f["e_loss"] > 0
+        return Res({"loss": loss, "count": count},
+                   lambda: {"loss": (np.array([f["ref"][0]]), 4 * f["e_loss"]), "count": exact(np.array([f["ref"][2]]))})
+    return Case(("jdet_kd_kl_div_level_forward",), "M %d K %d T %d %s" % (M, K, T, wmode), fn)
+
+
+def kl_backward_case(M, K, T, wmode, windowed=False, unaligned=False):
+    from tests import ld_ref as R
+    f = R.kl_fixture(M, K, T, wmode)
+    go = 0.75
+
+    def fn(run):
+        head, p = _kl_args(run, f, M, K, windowed, unaligned)
+        pad = 1 if unaligned else 0
+        count = run.inp("count", np.array([f["ref"][2]], np.int32), guard=1)
+        gout = run.inp("grad_out", np.array([go], np.float32))
+        grad = run.out("grad_pred", (M * K + pad,))
+        run.ok(lib().jdet_kd_kl_div_level_backward(*head, M, K, float(T), R.LOSS_WEIGHT, P(count), P(gout),
+                                                   P(grad) + 4 * pad, ST(p)), "jdet_kd_kl_div_level_backward")
+        if pad:
+            grad[:1].zero_()
+        ref = np.concatenate([np.zeros(pad), f["ref"][1].reshape(-1) * go])
+        print("kl backward M %d K %d T %d %s: bound %.3e" % (M, K, T, wmode, 4 * f["e_grad"]))
+        assert f["e_grad"] > 0
+
+        def err(v):                                          # unselected rows: exactly 0; the others within the bound
+            d = np.abs(v - ref)
+            if f["weight"] is not None and (f["weight"] > 0).any():
+                unsel = np.concatenate([np.zeros(pad, bool), np.repeat(f["weight"] <= 0, K)])
+                d[unsel] = np.where(v[unsel] == 0, 0.0, np.inf)
+            return d
+        return Res({"grad_pred": grad}, lambda: {"grad_pred": (err, 4 * f["e_grad"] * np.abs(ref).max())})
+    return Case(("jdet_kd_kl_div_level_backward",), "M %d K %d T %d %s" % (M, K, T, wmode), fn)
+
+
+# the smallest instances; the capped grids (60 000 anchors, 270 001 KL rows) stay parametrisations of tests/test_gpu_ld.py
+CASES.append(dist_integral_case(63, 8))
+CASES.append(dist_bbox_case(63, 8, 0.0, "ones"))
+CASES.append(kl_forward_case(64, 9, 2, "mixed", windowed=True))
+CASES.append(kl_backward_case(64, 9, 2, "mixed", windowed=True))

@@ -1,5 +1,5 @@
 """numpy restatement of ATSSAssignerRbbox.assign (python/jdet/models/boxes/assigner.py:L314-391 of the reference) with
-the rules include/jdet_hip_atss.h fixes where the reference leaves them open, and the fixtures of the ATSS tests.
+the rules include/jdet_hip.h fixes where the reference leaves them open, and the fixtures of the ATSS tests.
 
 What is fp32 here, in the stated order, is what the kernel computes in fp32: the centre distance
 sqrt(dx*dx + dy*dy), the serial sums of mean and unbiased variance, sqrt(max(var, 1e-6)) and the `>=` compare.  The IoU

@@ -1,7 +1,7 @@
 """Restatements of the rotated FCOS pieces, written from the reference's text, and the fixtures of the FCOS tests.
 
   targets(...)        FCOSHead._get_target_single (python/jdet/models/roi_heads/fcos_head.py:L599-670) + mintheta_obb
-                      (models/boxes/box_ops.py:L679-692) in numpy float64, with the rules include/jdet_hip_fcos.h fixes:
+                      (models/boxes/box_ops.py:L679-692) in numpy float64, with the rules include/jdet_hip.h fixes:
                       equal areas to the lower gt index, background rows zero, an image without gts all background.
                       It also returns the margins by which every decision clears its threshold.
   poly_iou_loss(...)  poly_iou_loss (models/losses/poly_iou_loss.py:L39-123) in torch, in float64 or float32: the tensor

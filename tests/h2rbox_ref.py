@@ -7,7 +7,7 @@
                      H2RBoxLoss.execute (models/losses/h2rbox_loss.py:L42-66), distance2obb (models/boxes/box_ops.py:
                      L694-707), bbox_overlaps(is_aligned=True) (models/boxes/iou_calculator.py:L302-342), iou_loss and
                      l1_loss, in torch, float64 or float32, LEVEL-major as the reference flattens, differentiated by
-                     autograd into BOTH views.  The rounding of the cell map is half-to-even (include/jdet_hip_h2rbox.h).
+                     autograd into BOTH views.  The rounding of the cell map is half-to-even (include/jdet_hip.h).
 
 Pinned by restatement only: Jittor is not importable here.  The loss fixtures are drawn and FILTERED here, at
 generation, so the tests drop no row: a cell whose rotated position is within 1e-3 of a rounding tie gets weight 0, and a

@@ -4,7 +4,7 @@ the weighted L1 / smooth-L1 on it and the knowledge-distillation KL divergence, 
 restatement's error against the float64 one).
 
 What the float64 side shares with every float32 implementation, because the C ABI takes them as floats: the bin values
-e_k = lo + k * ((hi - lo) / R) EVALUATED IN FP32 (include/jdet_hip_ld.h; exact at R = 8), beta, avg_factor, loss_weight
+e_k = lo + k * ((hi - lo) / R) EVALUATED IN FP32 (include/jdet_hip.h; exact at R = 8), beta, avg_factor, loss_weight
 and T as the float32 nearest to what the caller passes.
 
 Fixtures are seeded and cached; the arrays they return are shared and must not be written.  Conditions they meet by

@@ -1,4 +1,4 @@
-"""numpy restatement and fixtures of the Rotated RepPoints init-stage assignment (include/jdet_hip_reppoints.h:
+"""numpy restatement and fixtures of the Rotated RepPoints init-stage assignment (include/jdet_hip.h:
 jdet_convex_point_assign).
 
 `assign_loop` is ConvexAssigner.assign of the reference (models/boxes/assigner.py:L433-548) as its LITERAL sequential

@@ -51,6 +51,8 @@ def test_ctypes_signatures_match_header(built_lib):
     for name, nargs in d.items():
         assert len(built_lib.SIGNATURES[name][1]) == nargs, name
     lib = built_lib.lib()
+    for name, (res, args) in built_lib.SIGNATURES.items():
+        assert getattr(lib, name).argtypes == args and getattr(lib, name).restype == res, name
     assert lib.jdet_version() >= 1
     assert lib.jdet_nms_rotated_workspace(0) == 0
     assert lib.jdet_nms_rotated_workspace(65) >= 65 * 2 * 8 + 2 * 4

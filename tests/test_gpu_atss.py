@@ -135,35 +135,13 @@ def test_dense_head_route_equals_the_general_route(dev):
     assert np.array_equal(lab0, R.fixture("256a")[4]["labels"])
 
 
-def _contract_case(name, matrix):
-    from tests.abi_cases import I32, P, ST, Case, Res, exact
-    from jdet_amd import _lib as L
-    anchors, num_level, gts, labels, ref = R.fixture(name)
-    A, K, nl = anchors.shape[0], gts.shape[0], len(num_level)
-    offs = R.level_offsets(num_level)
-    ov0 = R.iou_matrix(anchors, gts) if matrix else None
-
-    def fn(run):
-        import ctypes
-        lib = L.lib()
-        a, g, gl = run.inp("anchors", anchors.copy()), run.inp("gt", gts.copy()), run.inp("gt_labels", labels.copy())
-        ov = run.inp("overlaps", ov0) if matrix else None
-        gt_inds, max_ov, lab = run.out("gt_inds", (A,), I32), run.out("max_overlaps", (A,)), run.out("labels", (A,), I32)
-        ws, wsb = run.ws("workspace", lib.jdet_atss_assign_workspace(A, K, nl, R.TOPK))
-        run.ok(lib.jdet_atss_assign(P(a), A, 5, (ctypes.c_int32 * (nl + 1))(*offs.tolist()), nl, P(g), K, P(gl), P(ov),
-                                    R.TOPK, 0, P(gt_inds), P(max_ov), P(lab), P(ws), wsb, ST(a)), "jdet_atss_assign")
-        return Res({"gt_inds": gt_inds, "max_overlaps": max_ov, "labels": lab},
-                   lambda: {"gt_inds": exact(ref["gt_inds"]), "max_overlaps": exact(ref["max_overlaps"]),
-                            "labels": exact(ref["labels"])})
-    return Case(("jdet_atss_assign",), "%s %s dirty workspace" % (name, "matrix" if matrix else "fused"), fn)
-
-
 @pytest.mark.parametrize("name,matrix", [("256a", False), ("256a", True), ("512b", False), ("512b", True)])
 def test_buffer_contract(dev, name, matrix):
     """guard bands, canaries, 0xFF workspace, B == A bit for bit, the restatement as the reference, and a workspace
     claim one byte short refused (tests/guarded.py)"""
     from tests import guarded
-    case = _contract_case(name, matrix)
+    from tests.abi_cases import atss_case
+    case = atss_case(name, matrix)
     guarded.run_case(case.entry_points[0], case.label, case.fn, dev)
 
 

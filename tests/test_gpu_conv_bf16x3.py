@@ -1,6 +1,5 @@
-"""GPU: the 3x3 convolution on bf16 MFMA through the exact three-way fp32 split (csrc/conv_bf16x3.hip,
-include/jdet_hip_bf16x3.h), called through its entry point: against float64 conv2d at the bound of
-tests/test_gpu_conv_igemm.py, against the fp32 kernel's own error, the bit-exact probes of tests/bf16x3_cases.py, the
+"""GPU: the 3x3 convolution on bf16 MFMA through the exact three-way fp32 split (csrc/conv_bf16x3.hip), called
+through its entry point: against float64 conv2d at the bound of tests/test_gpu_conv_igemm.py, against the fp32 kernel's own error, the bit-exact probes of tests/bf16x3_cases.py, the
 buffer contract, and the ConvModule route against JDET_CONV_BF16X3=0."""
 import numpy as np
 import pytest
@@ -112,25 +111,9 @@ def test_batch_of_zero_returns_at_once():
 def test_buffer_contract(dev, case):
     """the guard-band / poison protocol of tests/guarded.py: nothing outside y is written, no guard is read"""
     from tests import guarded
-    from tests.abi_cases import P as PTR, ST, Res
-    from jdet_amd import _lib as L
-    N, H, W, Cin, Cout = BC.CASES[case]
-    x0, w0, b0, mask0 = BC.inputs(case)
-
-    def fn(run):
-        x, w = run.inp("x", np.array(x0)), run.inp("w", np.array(w0))
-        b, mask = run.inp("bias", np.array(b0)), run.inp("rowmask", np.array(mask0))
-        y = run.out("y", (N, H, W, Cout))
-        run.ok(L.lib().jdet_conv3x3_bf16x3_forward(PTR(x), N, H, W, Cin, PTR(w), Cout, PTR(b), 1, PTR(mask), PTR(y),
-                                                   ST(x)), "jdet_conv3x3_bf16x3_forward")
-
-        def ref():
-            full = np.maximum(BC.reference(case, True), 0.0)
-            bound = BC.BOUND[0] * np.abs(full).max() + BC.BOUND[1]
-            return {"y": (_finish(BC.reference(case, True), True, mask0), bound)}
-        return Res({"y": y}, ref)
-
-    guarded.run_case("jdet_conv3x3_bf16x3_forward", "case " + case, fn, dev)
+    from tests.abi_cases import bf16x3_case
+    c = bf16x3_case(case)
+    guarded.run_case(c.entry_points[0], c.label, c.fn, dev)
 
 
 def test_conv_module_route_matches_the_fp32_route():

@@ -1,7 +1,8 @@
-"""GPU: the row-sparse backward of the regression towers' 3x3 convolutions (csrc/conv_rows.hip, include/jdet_hip_rows.h):
+"""GPU: the row-sparse backward of the regression towers' 3x3 convolutions (csrc/conv_rows.hip):
 the device-side row lists against numpy, both gradients against float64 conv2d autograd on the CPU at the bound of the
 igemm / weight-gradient tests (|err| <= 2e-5 max|ref| + 1e-6), exact zeros outside the dilated list, accumulation,
-count 0, the ConvModule route against the dense route, and a captured backward replayed with other gradients."""
+count 0, a data gradient without the zero fill, the ConvModule route against the dense route, and a captured backward
+replayed with other gradients."""
 import functools
 
 import numpy as np
@@ -243,3 +244,20 @@ def test_captured_backward_reads_the_count_at_replay(dev):
         for a, b in zip(out, ref):
             assert (a - b).abs().max().item() <= 2e-4 * b.abs().max().item() + 1e-6
     assert not any(o.any() for o in out[:1] + out[1::2])       # the last replay had no rows: zero input / weight gradients
+
+
+def test_dgrad_without_zero_fill_writes_the_listed_rows_only(dev):
+    """zero_first = 0: rows of gx outside the list keep what they held, bit for bit"""
+    from jdet_amd import _lib as L
+    from tests.abi_cases import ROWS_SHAPES, rows_inputs
+    N, H, W, Cin, Cout = ROWS_SHAPES[0]
+    x0, w0, g0, rows0, drows0 = rows_inputs(ROWS_SHAPES[0], 0.03)
+    g = torch.from_numpy(g0).to(dev)
+    wd = torch.from_numpy(np.ascontiguousarray(w0[:, :, ::-1, ::-1].transpose(1, 2, 3, 0))).to(dev)
+    rows, count = torch.from_numpy(drows0).to(dev), torch.tensor([len(drows0)], dtype=torch.int32, device=dev)
+    gx = torch.full((N * H * W, Cin), 3.25, device=dev)
+    L.check(L.lib().jdet_conv3x3_dgrad_rows(g.data_ptr(), wd.data_ptr(), rows.data_ptr(), count.data_ptr(), N, H, W, Cin,
+                                            Cout, 0, gx.data_ptr(), L.stream_ptr(g)), "jdet_conv3x3_dgrad_rows")
+    keep = torch.ones(N * H * W, dtype=torch.bool, device=dev)
+    keep[rows.long()] = False
+    assert bool((gx[keep] == 3.25).all()) and not bool((gx[~keep] == 3.25).all(1).any())

@@ -1,4 +1,4 @@
-"""GPU: the row-sparse forward of a regression tower's 3x3 convolutions (csrc/conv_rows.hip, include/jdet_hip_rows_fwd.h):
+"""GPU: the row-sparse forward of a regression tower's 3x3 convolutions (csrc/conv_rows.hip):
 the three device-side row lists from a flag byte per position against numpy, the gathered forward against float64
 conv2d + bias [+ relu] on the CPU at the bound of the igemm test (|err| <= 2e-5 max|ref| + 1e-6), untouched / zero rows
 outside the list, the row mask, count 0, a dense list, the two-layer tower + prediction layer against the dense route,

@@ -16,41 +16,15 @@ Loss.  257 rows (tests/fcos_ref.py: loss_fixture; 96 % of the drawn pairs pass t
 The float32 restatement differs from the float64 one on this fixture by 2.10e-05 in the loss and by 1.10e-04 of the
 row's max |g| in the gradient; the kernel may differ from float64 by 4 x that (a different, legal, operation order).
 Both reference errors are computed here from the restatements, never from the code under test."""
-import ctypes
-
 import numpy as np
 import pytest
 import torch
 
 from tests import fcos_ref as R
+from tests.abi_cases import (FCOS_CONTRACTS, fcos_centerness_bound as _centerness_bound, fcos_padded as _padded,
+                             fcos_ulp as _ulp)
 
 pytestmark = pytest.mark.gpu
-
-
-def _ulp(x):
-    return float(np.spacing(np.float32(abs(x))))
-
-
-def _padded(gts, labels, dev, poison=True):
-    """(B, Kmax, 5), (B, Kmax) int32, (B,) int32 on the device; the rows beyond an image's count hold NaN / a wild label"""
-    B, Kmax = len(gts), max(max(len(g) for g in gts), 1)
-    g = np.full((B, Kmax, 5), np.nan if poison else 0.0, np.float32)
-    lab = np.full((B, Kmax), 77 if poison else 0, np.int32)
-    for b in range(B):
-        g[b, :len(gts[b])] = gts[b]
-        lab[b, :len(gts[b])] = labels[b]
-    cnt = np.asarray([len(x) for x in gts], np.int32)
-    return torch.from_numpy(g).to(dev), torch.from_numpy(lab).to(dev), torch.from_numpy(cnt).to(dev)
-
-
-def _centerness_bound(ref, tol, norm_on_bbox):
-    """c = sqrt(m1/M1 * m2/M2) with every distance off by at most d: |dc| <= c * d * (1/m1 + 1/m2) to first order (doubled
-    here), + 4 ulp for the closed form itself; d = tol, divided by the stride where the targets are"""
-    t = ref["bbox_targets"]
-    d = tol / (np.asarray(R.STRIDES, np.float64)[R.points_of()[1]] if norm_on_bbox else 1.0)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        b = 2 * ref["centerness"] * d * (1 / np.minimum(t[:, 0], t[:, 2]) + 1 / np.minimum(t[:, 1], t[:, 3]))
-    return np.where(ref["inds"] >= 0, b + 4 * _ulp(1.0), 0.0)
 
 
 def _check_targets(out, gts, labels, norm_on_bbox, center_sampling):
@@ -207,61 +181,12 @@ def test_zero_weight_rows_cost_nothing_and_read_nothing(dev):
 
 
 # ----------------------------------------------------------------------------------------------------- buffer contracts
-def _targets_case(name, norm_on_bbox, center_sampling):
-    from tests.abi_cases import I32, P, ST, Case, Res, exact
-    from jdet_amd import _lib as L
-    gts, labels = R.target_fixture(name)
-    B, N = len(gts), 341
-    refs = [R.targets(g, gl, norm_on_bbox, center_sampling) for g, gl in zip(gts, labels)]
-    tol = 8 * _ulp(max([float(R.IMG)] + [float(np.abs(g[:, :4]).max()) for g in gts if len(g)]))
-    lv = (ctypes.c_int32 * 15)(*[int(v) for (h, w), s in zip(R.SIZES, R.STRIDES) for v in (h, w, s)])
-    rr = (ctypes.c_float * 10)(*[float(v) for r in R.RANGES for v in r])
-
-    def fn(run):
-        g0, l0, c0 = _padded(gts, labels, "cpu", poison=run.hostile)
-        g, gl, gc = run.inp("gt", g0.numpy()), run.inp("gt_labels", l0.numpy(), guard=99), run.inp("gt_count", c0.numpy(),
-                                                                                                   guard=100)
-        lab, tgt = run.out("labels", (B, N), I32), run.out("bbox_targets", (B, N, 5))
-        ctr, inds = run.out("centerness", (B, N)), run.out("gt_inds", (B, N), I32)
-        run.ok(L.lib().jdet_fcos_targets(lv, rr, 5, P(g), P(gl), P(gc), B, g0.shape[1], R.NUM_CLASSES, int(norm_on_bbox),
-                                         int(center_sampling), R.RADIUS, P(lab), P(tgt), P(ctr), P(inds), ST(g)),
-               "jdet_fcos_targets")
-        return Res({"labels": lab, "bbox_targets": tgt, "centerness": ctr, "gt_inds": inds},
-                   lambda: {"labels": exact(np.stack([r["labels"] for r in refs])),
-                            "gt_inds": exact(np.stack([r["inds"] for r in refs])),
-                            "bbox_targets": (np.stack([r["bbox_targets"] for r in refs]), tol),
-                            "centerness": (np.stack([r["centerness"] for r in refs]),
-                                           np.stack([_centerness_bound(r, tol, norm_on_bbox) for r in refs]))})
-    return Case(("jdet_fcos_targets",), "%s norm %d cs %d" % (name, norm_on_bbox, center_sampling), fn)
-
-
-def _loss_case(weighted):
-    from tests.abi_cases import P, ST, Case, Res
-    from jdet_amd import _lib as L
-    prd, tgt, _ = R.loss_fixture()
-    ref, e_loss, e_grad = R.loss_reference(False, weighted)
-    n = len(prd)
-
-    def fn(run):
-        p, t = run.inp("pred", np.array(prd)), run.inp("target", np.array(tgt))
-        w = run.inp("weight", np.array(R.loss_weights())) if weighted else None
-        loss, grad = run.out("loss", (n,)), run.out("grad_pred", (n, 5))
-        run.ok(L.lib().jdet_poly_iou_loss(P(p), P(t), P(w), n, 0, 1e-6, P(loss), P(grad), ST(p)), "jdet_poly_iou_loss")
-        gmax = np.abs(ref["grad"]).max(1, keepdims=True)
-        return Res({"loss": loss, "grad_pred": grad},
-                   lambda: {"loss": (ref["loss"], 4 * e_loss),
-                            "grad_pred": (ref["grad"], np.broadcast_to(4 * e_grad * gmax, ref["grad"].shape).copy())})
-    return Case(("jdet_poly_iou_loss",), "257 rows%s" % (" weighted" if weighted else ""), fn)
-
-
 @pytest.mark.parametrize("case", ["targets k7_k0", "targets k7_k0 cs", "targets k70 cs", "loss", "loss weighted"])
 def test_buffer_contract(dev, case):
     """guard bands, canaries, B == A bit for bit with poisoned outputs and NaN gt rows beyond the count, the restatement
     as the reference (tests/guarded.py)"""
     from tests import guarded
-    c = {"targets k7_k0": lambda: _targets_case("k7_k0", True, False), "targets k7_k0 cs": lambda: _targets_case("k7_k0", True, True),
-         "targets k70 cs": lambda: _targets_case("k70", False, True),
-         "loss": lambda: _loss_case(False), "loss weighted": lambda: _loss_case(True)}[case]()
+    c = FCOS_CONTRACTS[case]()
     guarded.run_case(c.entry_points[0], c.label, c.fn, dev)
 
 

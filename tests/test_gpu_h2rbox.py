@@ -16,7 +16,6 @@ restatements, never from the code under test, and printed:
                 fixture applies, uses the largest of the six.
 aug_index is compared exactly.  The losing branch's gradient is absent from the float64 reference (autograd through
 torch.minimum of the two scalars), so the gradient comparison is also the test of its absence."""
-import ctypes
 import math
 
 import numpy as np
@@ -24,15 +23,13 @@ import pytest
 import torch
 
 from tests import h2rbox_ref as R
+from tests.abi_cases import H2RBOX_CONTRACTS as CONTRACTS, H2RBOX_FRAMES as FRAMES
 
 pytestmark = pytest.mark.gpu
 
 FIXTURES = [(rot, win) for rot in R.ROTS for win in (1, 2)]
 IDS = ["rot%.2f-branch%d" % f for f in FIXTURES]
 ANGLES = (0.0, math.pi / 2, -math.pi / 2, math.pi, 0.3, -2.5)
-# the issue's two frames, and the non-square one again with a margin of 1 px: there every padding rule acts where H != W
-FRAMES = {"37x37->32x32": ((37, 37), (32, 32)), "40x56->24x40": ((40, 56), (24, 40)),
-          "40x56->38x54": ((40, 56), (38, 54))}
 
 
 def detector_loss_bound():
@@ -211,120 +208,6 @@ def test_dense_route_of_the_loss_against_its_general_route(dev, rot, win):
 
 
 # ----------------------------------------------------------------------------------------------------- buffer contracts
-def _levels():
-    lv = (ctypes.c_int32 * (3 * len(R.SIZES)))(*[int(v) for (h, w), s in zip(R.SIZES, R.STRIDES) for v in (h, w, s)])
-    ag = (ctypes.c_int32 * len(R.AGNOSTIC))(*R.AGNOSTIC)
-    return lv, ag
-
-
-def _rotate_case(frame, theta, padding):
-    from tests.abi_cases import P, ST, Case, Res, exact
-    from jdet_amd import _lib as L
-    from jdet_amd.ops.rotate_crop import PADDING
-    (h, w), size = FRAMES[frame]
-    img = R.image_fixture(h, w)
-
-    def fn(run):
-        x = run.inp("img", img.copy())
-        out = run.out("out", (2, 3) + size)
-        cs, sn = (1.0, 0.0) if theta == 0 else (math.cos(theta), math.sin(theta))
-        run.ok(L.lib().jdet_rotate_crop(P(x), 2, 3, h, w, size[0], size[1], cs, sn, PADDING[padding], P(out), ST(x)),
-               "jdet_rotate_crop")
-        if theta == 0:
-            ch, cw = (h - size[0]) // 2, (w - size[1]) // 2
-            return Res({"out": out}, lambda: {"out": exact(img[..., ch:ch + size[0], cw:cw + size[1]])})
-        ref, e32 = R.rotate_crop_reference(h, w, size, theta, padding)
-        return Res({"out": out}, lambda: {"out": (ref, 4 * e32)})
-    return Case(("jdet_rotate_crop",), "%s theta %.1f %s" % (frame, theta, padding), fn)
-
-
-def _aug_args(run, rot, win, hostile_rows):
-    from tests.abi_cases import P
-    pred, pred_aug, weight, labels, _ = R.loss_fixture(rot, win)
-    ref = R.loss_reference(rot, win)[0]
-    p1, p2 = pred.copy(), pred_aug.copy()
-    if hostile_rows and run.hostile:                         # the rows nobody may read hold NaN in the hostile runs
-        hit = np.zeros((R.B, R.N), bool)
-        for b in range(R.B):
-            hit[b, ref["aug_index"][b][ref["aug_index"][b] >= 0]] = True
-        p1[weight == 0] = np.nan
-        p2[~hit] = np.nan
-    lv, ag = _levels()
-    t = [run.inp("pred", p1), run.inp("pred_aug", p2), run.inp("weight", weight.copy()),
-         run.inp("labels", labels.copy(), guard=99)]
-    rf = R.f32(rot)
-    head = (lv, len(R.SIZES), P(t[0]), P(t[1]), P(t[2]), P(t[3]), ag, len(R.AGNOSTIC), R.B, rf, math.cos(rf), math.sin(rf),
-            R.CROP[0], R.CROP[1], R.WEIGHTS["shape"], R.WEIGHTS["angle"], R.EPS)
-    return head, t, ref, (pred, pred_aug, weight, labels)
-
-
-def _terms64(ref, data, rot):
-    """the error measure of `terms` for the contract rows: exact zeros in the rows that take no part, the weight in
-    column 3 and finite, non-negative terms in the valid rows (the VALUES are held to the float64 column sums in
-    test_aug_terms_select_the_scalar_minimum and, through the loss, in the float64 comparison above; the contract row
-    adds the guard bands, the full overwrite and B == A bit for bit with NaN in the rows nobody may read)"""
-    pred, pred_aug, weight, labels = data
-    valid = ref["aug_index"] >= 0
-
-    def err(v):
-        v = v.reshape(R.B, R.N, 4)
-        bad = np.zeros_like(v)
-        bad[~valid] = np.abs(v[~valid])                      # must be 0
-        bad[valid, 3] = np.abs(v[valid, 3] - weight[valid])  # must be the weight
-        bad[valid, :3] = np.where(np.isfinite(v[valid, :3]) & (v[valid, :3] >= 0), 0.0, 1.0)
-        return bad
-    return err
-
-
-def _forward_case(rot, win):
-    from tests.abi_cases import I32, P, ST, Case, Res, exact
-    from jdet_amd import _lib as L
-
-    def fn(run):
-        head, t, ref, data = _aug_args(run, rot, win, True)
-        terms, idx = run.out("terms", (R.B, R.N, 4)), run.out("aug_index", (R.B, R.N), I32)
-        run.ok(L.lib().jdet_h2rbox_aug_loss_forward(*head, P(terms), P(idx), ST(t[0])), "jdet_h2rbox_aug_loss_forward")
-        return Res({"terms": terms, "aug_index": idx},
-                   lambda: {"aug_index": exact(ref["aug_index"]), "terms": (_terms64(ref, data, rot), 0.0)})
-    return Case(("jdet_h2rbox_aug_loss_forward",), "rot %.1f branch %d" % (rot, win), fn)
-
-
-def _backward_case(rot, win):
-    from tests.abi_cases import I32, P, ST, Case, Res
-    from jdet_amd import _lib as L
-
-    def fn(run):
-        head, t, ref, data = _aug_args(run, rot, win, True)
-        _, e_loss, e_g1, e_g2 = R.loss_reference(rot, win)
-        scale = R.WEIGHTS["loss_weight"] / ref["avg"]
-        idx = run.inp("aug_index", ref["aug_index"].copy(), guard=100)
-        br = run.inp("branch", np.array([win - 1], np.int32), guard=101)
-        sc = run.inp("scale_centre", np.array([scale * R.WEIGHTS["centre"]], np.float32))
-        sb = run.inp("scale_branch", np.array([scale], np.float32))
-        g1, g2 = run.out("grad_pred", (R.B, R.N, 5)), run.out("grad_pred_aug", (R.B, R.N, 5))
-        scratch = run.out("contrib", (R.B, R.N, 5))
-        run.ok(L.lib().jdet_h2rbox_aug_loss_backward(*head, P(idx), P(br), P(sc), P(sb), P(g1), P(g2), P(scratch),
-                                                     ST(t[0])), "jdet_h2rbox_aug_loss_backward")
-        # the scales enter as float32: one more rounding each (2^-24 relative) on top of the gradient bound
-        m1, m2 = np.abs(ref["grad_pred"]).max(), np.abs(ref["grad_aug"]).max()
-        return Res({"grad_pred": g1, "grad_pred_aug": g2},
-                   lambda: {"grad_pred": (ref["grad_pred"], (4 * e_g1 + 2.0 ** -23) * m1),
-                            "grad_pred_aug": (ref["grad_aug"], (4 * e_g2 + 2.0 ** -23) * m2)})
-    return Case(("jdet_h2rbox_aug_loss_backward",), "rot %.1f branch %d" % (rot, win), fn)
-
-
-CONTRACTS = {
-    "rotate 37 reflection": lambda: _rotate_case("37x37->32x32", -2.5, "reflection"),
-    "rotate 40x56 zeros": lambda: _rotate_case("40x56->24x40", 0.3, "zeros"),
-    "rotate 40x56 copy": lambda: _rotate_case("40x56->24x40", 0.0, "border"),
-    "rotate 40x56 thin border": lambda: _rotate_case("40x56->38x54", -2.5, "border"),
-    "forward branch 1": lambda: _forward_case(0.3, 1),
-    "forward branch 2": lambda: _forward_case(-2.5, 2),
-    "backward branch 1": lambda: _backward_case(0.3, 1),
-    "backward branch 2": lambda: _backward_case(math.pi / 2, 2),
-}
-
-
 @pytest.mark.parametrize("case", sorted(CONTRACTS))
 def test_buffer_contract(dev, case):
     """guard bands, canaries, B == A bit for bit with poisoned outputs and NaN in the rows nobody may read

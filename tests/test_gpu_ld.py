@@ -24,6 +24,8 @@ import pytest
 import torch
 
 from tests import ld_ref as R
+from tests.abi_cases import (dist_bbox_case as _bbox_case, kl_backward_case as _kl_backward_case,
+                             kl_forward_case as _kl_forward_case)
 
 pytestmark = pytest.mark.gpu
 
@@ -81,53 +83,6 @@ def test_integral_against_float64(dev, reg_max):
 
 
 # ------------------------------------------------------------------------------------------------- distribution loss
-def _bbox_case(rows, reg_max, beta, wmode, windowed=False, unaligned=False):
-    """contract row of jdet_dist_bbox_loss_level.  windowed: rows = 2 n, target / weight the windows [:, 7:7 + n] of
-    (2, n + 69, 5) arrays whose other rows are NaN; unaligned: logits and gradient 4 bytes off a 16-byte boundary.
-    Hostile runs: NaN in the logits of rows whose five weights are 0 and in the targets of weight 0."""
-    from tests.abi_cases import P, ST, Case, Res, exact
-    from jdet_amd import _lib as L
-    f = R.bbox_fixture(rows, reg_max, beta, "ones" if wmode == "zeros" else wmode)
-    weight = np.zeros_like(f["weight"]) if wmode == "zeros" else f["weight"]
-    K5 = 5 * (reg_max + 1)
-
-    def fn(run):
-        x, t = f["logits"].copy(), f["target"].copy()
-        if run.hostile:
-            x[(weight == 0).all(axis=1)] = np.nan
-            t[weight == 0] = np.nan
-        n, total, start, blocks = rows, rows, 0, 1
-        tw = [t, weight]
-        if windowed:
-            blocks, n = 2, rows // 2
-            total, start = n + 69, 7
-            tw = [R.window(a.reshape(2, n, 5), total, start) for a in tw]
-        pad = 1 if unaligned else 0
-        xin = run.inp("logits", np.concatenate([np.zeros(pad, np.float32), x.reshape(-1)]))
-        tin, win = run.inp("target", tw[0]), run.inp("weight", tw[1])
-        avg = run.inp("avg_factor", np.array([R.AVG], np.float32))
-        loss, grad = run.out("loss", (1,)), run.out("grad_logits", (rows * K5 + pad,))
-        ws, wsb = run.ws("workspace", L.lib().jdet_sigmoid_focal_loss_workspace())
-        off = start * 5 * 4
-        run.ok(L.lib().jdet_dist_bbox_loss_level(
-            P(xin) + 4 * pad, P(tin) + off, n, total, P(win) + off, n, total, rows, reg_max, *R.ENDS, *R.ANGLE_ENDS,
-            float(beta), P(avg), R.LOSS_WEIGHT, P(loss), P(grad) + 4 * pad, P(ws), wsb, ST(xin)),
-            "jdet_dist_bbox_loss_level")
-        if pad:                                              # the word in front of the unaligned gradient is nobody's
-            grad[:1].zero_()
-        if wmode == "zeros":
-            return Res({"loss": loss, "grad_logits": grad},
-                       lambda: {"loss": exact(np.zeros(1)), "grad_logits": exact(np.zeros(rows * K5 + pad))})
-        unit = np.concatenate([np.zeros(pad), f["ref"][1].reshape(-1) * (R.AVG / R.LOSS_WEIGHT)])
-        print("bbox rows %d reg_max %d beta %.3f %s: bounds loss %.3e grad %.3e" % (rows, reg_max, beta, wmode, 4 * f["e_loss"], 4 * f["e_grad"]))
-        assert f["e_loss"] > 0 and f["e_grad"] > 0
-        return Res({"loss": loss, "grad_logits": grad},
-                   lambda: {"loss": (np.array([f["ref"][0]]), 4 * f["e_loss"]),
-                            "grad_logits": (unit, 4 * f["e_grad"] * np.abs(unit).max())})
-    return Case(("jdet_dist_bbox_loss_level",), "rows %d R %d beta %.2f %s%s%s" % (
-        rows, reg_max, beta, wmode, " window" if windowed else "", " unaligned" if unaligned else ""), fn)
-
-
 @pytest.mark.parametrize("reg_max", [1, 8, 31])
 @pytest.mark.parametrize("rows", [1, 63, 257, 2 * 1531])
 def test_bbox_loss_contract_and_float64(dev, rows, reg_max):
@@ -184,79 +139,6 @@ def test_bbox_node_against_float64_and_the_composed_route(dev, beta, monkeypatch
 
 
 # -------------------------------------------------------------------------------------------------------- KL divergence
-def _blocks(M):
-    return 5 if M % 5 == 0 and M > 5 else (4 if M % 4 == 0 and M > 4 else 1)
-
-
-def _kl_args(run, f, M, K, windowed, unaligned=False):
-    """inputs of both KL entry points -> (pred, soft, weight pointer, rows_per_block, block_stride, tensors)"""
-    from tests.abi_cases import P
-    pred, soft, weight = f["pred"].copy(), f["soft"].copy(), f["weight"]
-    if run.hostile and weight is not None and (weight > 0).any():
-        pred[weight <= 0] = np.nan                           # rows nobody may use
-        soft[weight <= 0] = np.nan
-    pad = 1 if unaligned else 0
-    p = run.inp("pred", np.concatenate([np.zeros(pad, np.float32), pred.reshape(-1)]))
-    s = run.inp("soft", np.concatenate([np.zeros(pad, np.float32), soft.reshape(-1)]))
-    if weight is None:
-        return (P(p) + 4 * pad, P(s) + 4 * pad, None, 1, 0), p
-    if windowed:
-        B = _blocks(M)
-        n = M // B
-        w = run.inp("weight", R.window(weight.reshape(B, n), n + 13, 3))
-        return (P(p) + 4 * pad, P(s) + 4 * pad, P(w) + 3 * 4, n, n + 13), p
-    w = run.inp("weight", weight)
-    return (P(p) + 4 * pad, P(s) + 4 * pad, P(w), M, M), p
-
-
-def _kl_forward_case(M, K, T, wmode, windowed=False, unaligned=False):
-    from tests.abi_cases import I32, P, ST, Case, Res, exact
-    from jdet_amd import _lib as L
-    f = R.kl_fixture(M, K, T, wmode)
-
-    def fn(run):
-        head, p = _kl_args(run, f, M, K, windowed, unaligned)
-        loss, count = run.out("loss", (1,)), run.out("count", (1,), I32)
-        ws, wsb = run.ws("workspace", L.lib().jdet_sigmoid_focal_loss_workspace())
-        run.ok(L.lib().jdet_kd_kl_div_level_forward(*head, M, K, float(T), R.LOSS_WEIGHT, P(loss), P(count), P(ws), wsb,
-                                                    ST(p)), "jdet_kd_kl_div_level_forward")
-        print("kl forward M %d K %d T %d %s: bound %.3e" % (M, K, T, wmode, 4 * f["e_loss"]))
-        assert f["e_loss"] > 0
-        return Res({"loss": loss, "count": count},
-                   lambda: {"loss": (np.array([f["ref"][0]]), 4 * f["e_loss"]), "count": exact(np.array([f["ref"][2]]))})
-    return Case(("jdet_kd_kl_div_level_forward",), "M %d K %d T %d %s" % (M, K, T, wmode), fn)
-
-
-def _kl_backward_case(M, K, T, wmode, windowed=False, unaligned=False):
-    from tests.abi_cases import P, ST, Case, Res
-    from jdet_amd import _lib as L
-    f = R.kl_fixture(M, K, T, wmode)
-    go = 0.75
-
-    def fn(run):
-        head, p = _kl_args(run, f, M, K, windowed, unaligned)
-        pad = 1 if unaligned else 0
-        count = run.inp("count", np.array([f["ref"][2]], np.int32), guard=1)
-        gout = run.inp("grad_out", np.array([go], np.float32))
-        grad = run.out("grad_pred", (M * K + pad,))
-        run.ok(L.lib().jdet_kd_kl_div_level_backward(*head, M, K, float(T), R.LOSS_WEIGHT, P(count), P(gout),
-                                                     P(grad) + 4 * pad, ST(p)), "jdet_kd_kl_div_level_backward")
-        if pad:
-            grad[:1].zero_()
-        ref = np.concatenate([np.zeros(pad), f["ref"][1].reshape(-1) * go])
-        print("kl backward M %d K %d T %d %s: bound %.3e" % (M, K, T, wmode, 4 * f["e_grad"]))
-        assert f["e_grad"] > 0
-
-        def err(v):                                          # unselected rows: exactly 0; the others within the bound
-            d = np.abs(v - ref)
-            if f["weight"] is not None and (f["weight"] > 0).any():
-                unsel = np.concatenate([np.zeros(pad, bool), np.repeat(f["weight"] <= 0, K)])
-                d[unsel] = np.where(v[unsel] == 0, 0.0, np.inf)
-            return d
-        return Res({"grad_pred": grad}, lambda: {"grad_pred": (err, 4 * f["e_grad"] * np.abs(ref).max())})
-    return Case(("jdet_kd_kl_div_level_backward",), "M %d K %d T %d %s" % (M, K, T, wmode), fn)
-
-
 @pytest.mark.parametrize("T", [1, 2, 10])
 @pytest.mark.parametrize("K", [2, 9, 15, 32])
 def test_kl_contract_and_float64(dev, K, T):

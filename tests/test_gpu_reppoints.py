@@ -5,13 +5,12 @@ detector built from REPPOINTS_CFG: training steps, no host sync on the dense rou
 
 The GIoU and its raw gradient are pinned against oracle/convex_giou_oracle.py by tests/test_gpu_convex_ops.py; nothing
 of that is repeated here."""
-import ctypes
-
 import numpy as np
 import pytest
 import torch
 
 from tests import reppoints_ref as R
+from tests.abi_cases import REPPOINTS_CONTRACTS, giou_general_rows as _general_rows, giou_loss_rows as _loss_rows
 
 pytestmark = pytest.mark.gpu
 
@@ -134,32 +133,6 @@ def test_general_assigner_entry_reads_the_stride_column(dev):
 
 
 # ------------------------------------------------------------------------------------------------------------------ loss
-def _loss_rows(seed=5, P=300, n_pos=100):
-    """pred (P, 18), target (P, 8), weight (P), norm (P): n_pos positive rows at random positions (a rotated box and
-    nine points scattered over it), the rest weight 0 with NaN in pred and target; norm per row in {16, 32, 64}"""
-    rng = np.random.default_rng(seed)
-    pos = np.sort(rng.choice(P, n_pos, replace=False))
-    norm = rng.choice(np.asarray([16.0, 32.0, 64.0], np.float32), P).astype(np.float32)
-    pred = np.full((P, 18), np.nan, np.float32)
-    target = np.full((P, 8), np.nan, np.float32)
-    weight = np.zeros(P, np.float32)
-    c = rng.uniform(50, 200, (n_pos, 2))
-    wh = np.exp(rng.uniform(np.log(16.0), np.log(160.0), (n_pos, 2)))
-    target[pos] = R.obb_poly(c, wh, rng.uniform(-np.pi / 2, np.pi / 2, n_pos))
-    spread = rng.uniform(0.15, 0.8, (n_pos, 1, 1)) * wh.mean(1)[:, None, None]
-    shift = rng.uniform(-0.5, 0.5, (n_pos, 1, 2)) * wh[:, None, :]
-    pred[pos] = (c[:, None, :] + shift + rng.normal(0, 1, (n_pos, 9, 2)) * spread).reshape(n_pos, 18).astype(np.float32)
-    weight[pos] = rng.uniform(0.5, 2.0, n_pos).astype(np.float32)
-    return pred, target, weight, norm, pos
-
-
-def _general_rows(pred, target, weight, norm):
-    """the general route on device tensors of the positive rows: torch fp32 division, reppoints_convex_giou, the rule"""
-    from jdet_amd.models.losses.convex_giou_loss import convex_giou_rows
-    loss, grad = convex_giou_rows(pred / norm[:, None], target / norm[:, None], weight)
-    return loss, grad / norm[:, None]
-
-
 def _bits(t):
     return t.contiguous().view(torch.int32)
 
@@ -253,68 +226,12 @@ def test_dense_loss_empty_and_module_entries(dev):
 
 
 # ----------------------------------------------------------------------------------------------------- buffer contracts
-def _assign_case(name, pos_num, with_labels, stride):
-    from tests.abi_cases import I32, P, ST, Case, Res, exact
-    from jdet_amd import _lib as L
-    fx = R.fixture(name)
-    B, Kmax, N = fx["gt"].shape[0], fx["gt"].shape[1], len(fx["points"])
-    refs = [R.assign_loop(fx["points"], fx["sizes"], fx["level_ids"], fx["gt"][b, :k], fx["labels"][b, :k],
-                          pos_num=pos_num, labels_filled=-1) for b, k in enumerate(fx["counts"])]
-    offs = (ctypes.c_int32 * 6)(*np.concatenate([[0], np.cumsum(fx["sizes"])]).tolist())
-    ids = (ctypes.c_int32 * 5)(*fx["level_ids"])
-
-    def fn(run):
-        gt = fx["gt"].copy()
-        if run.hostile:                                     # rows beyond an image's count are never read
-            for b, k in enumerate(fx["counts"]):
-                gt[b, k:] = np.nan
-        pts = run.strided("points", fx["points"], stride)
-        g, gl = run.inp("gt", gt), run.inp("gt_labels", fx["labels"], guard=99)
-        gc = run.inp("gt_count", np.asarray(fx["counts"], np.int32), guard=100)
-        gi = run.out("gt_inds", (B, N), I32)
-        lab = run.out("labels", (B, N), I32) if with_labels else None
-        ws, wsb = run.ws("workspace", L.lib().jdet_convex_point_assign_workspace(B, N))
-        run.ok(L.lib().jdet_convex_point_assign(P(pts), N, stride, offs, ids, 5, P(g), P(gl) if with_labels else None,
-                                                P(gc), B, Kmax, R.SCALE, pos_num, -1, P(gi), P(lab), P(ws), wsb, ST(g)),
-               "jdet_convex_point_assign")
-        outs = {"gt_inds": gi}
-        want = {"gt_inds": exact(np.stack([r["gt_inds"] for r in refs]))}
-        if with_labels:
-            outs["labels"] = lab
-            want["labels"] = exact(np.stack([r["labels"] for r in refs]))
-        return Res(outs, lambda: want)
-    return Case(("jdet_convex_point_assign",), "%s pos_num %d%s stride %d" % (name, pos_num,
-                                                                               " labels" if with_labels else "", stride), fn)
-
-
-def _loss_case(dev):
-    from tests.abi_cases import P, ST, Case, Res, exact
-    from jdet_amd import _lib as L
-    pred, target, weight, norm, pos = _loss_rows(seed=7, P=131, n_pos=40)
-    t = lambda a: torch.from_numpy(a).to(dev)  # noqa: E731
-    ref_loss, ref_grad = _general_rows(t(pred[pos]), t(target[pos]), t(weight[pos]), t(norm[pos]))
-    want_loss, want_grad = np.zeros(131, np.float32), np.zeros((131, 18), np.float32)
-    want_loss[pos], want_grad[pos] = ref_loss.cpu().numpy(), ref_grad.cpu().numpy()
-
-    def fn(run):
-        nm = norm.copy()
-        if run.hostile:                                     # a row of weight 0 does not read its norm either
-            nm[weight == 0] = np.nan
-        p, tg, w, n = run.inp("pred", pred), run.inp("target", target), run.inp("weight", weight), run.inp("norm", nm)
-        loss, grad = run.out("loss", (131,)), run.out("grad_pred", (131, 18))
-        run.ok(L.lib().jdet_convex_giou_loss(P(p), P(tg), P(w), P(n), 131, P(loss), P(grad), ST(p)),
-               "jdet_convex_giou_loss")
-        return Res({"loss": loss, "grad_pred": grad}, lambda: {"loss": exact(want_loss), "grad_pred": exact(want_grad)})
-    return Case(("jdet_convex_giou_loss",), "131 rows, 40 positive", fn)
-
-
 @pytest.mark.parametrize("case", ["assign b2_256", "assign k70_k0", "loss"])
 def test_buffer_contract(dev, case):
     """guard bands, canaries, a 0xFF workspace, one byte short refused, B == A bit for bit with poisoned outputs, NaN
     in the gt rows beyond the count and in the unused point columns (tests/guarded.py)"""
     from tests import guarded
-    c = {"assign b2_256": lambda: _assign_case("b2_256", 3, True, 4), "assign k70_k0": lambda: _assign_case("k70_k0", 1, False, 2),
-         "loss": lambda: _loss_case(dev)}[case]()
+    c = REPPOINTS_CONTRACTS[case]()
     guarded.run_case(c.entry_points[0], c.label, c.fn, dev)
 
 

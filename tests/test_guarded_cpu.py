@@ -115,7 +115,10 @@ def test_same_bits_sees_signed_zero_and_nan_payloads():
     assert G.compare_runs({"y": a}, {"y": a.clone()}) == []
 
 
-EXEMPT_PATTERNS = ("jdet_version", "*_workspace", "*_supported", "*_rows", "*_bytes", "jdet_zero_fill",
+# the two *_rows names are size queries; a "*_rows" pattern would also take in jdet_conv3x3_wgrad_rows / _dgrad_rows,
+# which launch kernels
+EXEMPT_PATTERNS = ("jdet_version", "*_workspace", "*_supported", "jdet_conv_bn_sums_rows",
+                   "jdet_bn_act_backward_from_output_rows", "jdet_conv3x3_wgrad_rows_workers", "*_bytes", "jdet_zero_fill",
                    "jdet_graph_replace_memset_nodes", "jdet_roi_align_*", "jdet_roi_spatial_order")
 
 
