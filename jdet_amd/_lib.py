@@ -184,6 +184,19 @@ SIGNATURES = {
     "jdet_conv3x3_bf16x3_forward": (_i, [_p, _i, _i, _i, _i, _p, _i, _p, _i, _p, _p, _p]),
 }
 
+# mirrors include/jdet_hip_retina.h one to one (tests/test_retinanet_cpu.py checks it): RetinaNet-v1d's gt preparation,
+# one-pass targets, decode / threshold compaction and the bilinear FPN merge; same library, its own header
+RETINA_SIGNATURES = {
+    "jdet_retina_gt_prepare": (_i, [_p, _i, _p, _p, _p]),
+    "jdet_retina_targets_workspace": (_sz, [_i, _i]),
+    "jdet_retina_targets": (_i, [_p, _i, _p, _p, _p, _p, _i, _i, _f, _f, _f, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "jdet_retina_detect_workspace": (_sz, [_i, _i]),
+    "jdet_retina_detect_count": (_i, [_p, _p, _p, _i, _i, _f, _p, _p, _sz, _p]),
+    "jdet_retina_detect_fill": (_i, [_p, _p, _p, _i, _i, _f, _f, _f, _p, _sz, _i, _p, _p, _p, _p]),
+    "jdet_upsample_add_bilinear_nhwc_forward": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _f, _p, _p]),
+    "jdet_upsample_add_bilinear_nhwc_backward": (_i, [_p, _i, _i, _i, _i, _i, _i, _f, _p, _p]),
+}
+
 _lib = None
 
 # Hull-point ordering inside the rotated IoU: 0 = the reference's CPU path (std::sort,
@@ -214,7 +227,7 @@ def lib():
         # process and our DT_NEEDED entry resolves to that same runtime: one HIP context, shared
         # streams and allocations.
         l = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(RETINA_SIGNATURES.items()):
             fn = getattr(l, name)  # AttributeError here == ABI drift: fail loudly
             fn.restype = res
             fn.argtypes = args

@@ -344,3 +344,32 @@ LD_RETINANET_CFG = _ld_retinanet_cfg(
     loss_im=dict(type="IMLoss", loss_weight=0), imitation_method="finegrained", reg_max=8)
 LD_RETINANET_CFG["model"] = dict(LD_RETINANET_CFG["model"], type="KnowledgeDistillationSingleStageDetector",
                                  teacher_config=DIST_RETINANET_R50_CFG, teacher_ckpt=None)
+
+
+# ---- the reference's own RetinaNet (configs/retinanet_r50v1d_fpn_{dota,dota1_5,fair}.py): Resnet50_v1d, a bilinear FPN
+# merge halved at every step, RetinaHead on 21 horizontal anchors per location.  The three files differ in n_class only
+# (dota1_5 says 15, as dota does).  tests/golden/configs/retinanet_r50v1d_fpn_*.yaml hold them as `Config` reads them.
+def _retinanet_v1d_cfg(n_class):
+    return dict(
+        model=dict(
+            type="RetinaNet",
+            backbone=dict(type="Resnet50_v1d", return_stages=["layer1", "layer2", "layer3", "layer4"], pretrained=True),
+            neck=dict(type="FPN", in_channels=[256, 512, 1024, 2048], out_channels=256, start_level=1,
+                      add_extra_convs="on_output", num_outs=5, upsample_cfg=dict(mode="bilinear", tf_mode=True),
+                      upsample_div_factor=2, relu_before_extra_convs=True),
+            rpn_net=dict(
+                type="RetinaHead", n_class=n_class, in_channels=256, stacked_convs=4, mode="R", score_threshold=0.05,
+                nms_iou_threshold=0.3, max_dets=10000, roi_beta=1 / 9., cls_loss_weight=1., loc_loss_weight=0.2,
+                anchor_generator=dict(
+                    type="AnchorGeneratorRotated", strides=[8, 16, 32, 64, 128],
+                    ratios=[1, 0.5, 2.0, 0.3333333333333333, 3.0, 5.0, 0.2],
+                    scales=[1, 1.2599210498948732, 1.5874010519681994], base_sizes=[32, 64, 128, 256, 512],
+                    angles=[-90, -75, -60, -45, -30, -15], mode="H"))),
+        optimizer=dict(type="GradMutilpySGD", lr=3 * 5e-4, momentum=0.9, weight_decay=1e-4,
+                       grad_clip=dict(max_norm=30., norm_type=2)),
+        scheduler=dict(type="StepLR", warmup="linear", warmup_iters=14000, warmup_ratio=0.1, milestones=[27]))
+
+
+RETINANET_V1D_DOTA_CFG = _retinanet_v1d_cfg(15)
+RETINANET_V1D_DOTA1_5_CFG = _retinanet_v1d_cfg(15)
+RETINANET_V1D_FAIR_CFG = _retinanet_v1d_cfg(37)

@@ -113,6 +113,78 @@ class AnchorGeneratorRotatedRetinaNet(_RotatedLattice):
 
 
 @BOXES.register_module()
+class AnchorGeneratorRotated:
+    """Multi-level corner anchors of RetinaHead (anchor_generator.py:L599-752): mode "H" gives <x0, y0, x1, y1> around
+    center_offset * base_size (the given `angles` are ignored), mode "R" the same four columns plus an angle column.
+    The reference's ordering quirk is kept: ratio-major only when `scale_major and mode == "R"`; in mode "H" the scales
+    are the outer loop and the ratios the inner one.  fp32 products in the reference's order: ((base * first factor) *
+    second factor) * 1."""
+
+    def __init__(self, strides, ratios, scales, base_sizes=None, angles=[0, ], scale_major=True, centers=None,
+                 center_offset=0.5, mode="H"):
+        assert mode in ["H", "R"]
+        self.ratios = torch.as_tensor(ratios, dtype=torch.float32)
+        self.scales = torch.as_tensor(scales, dtype=torch.float32)
+        self.strides = [(stride, stride) for stride in strides]
+        self.base_sizes = [min(stride) for stride in self.strides] if base_sizes is None else base_sizes
+        self.mode = mode
+        self.angles = torch.as_tensor(angles if mode == "R" else [0.], dtype=torch.float32)
+        self.scale_major, self.centers, self.center_offset = scale_major, centers, center_offset
+        self.base_anchors = self.gen_base_anchors()
+        self._lattices = {}
+
+    @property
+    def num_base_anchors(self):
+        return [b.size(0) for b in self.base_anchors]
+
+    @property
+    def num_levels(self):
+        return len(self.strides)
+
+    def gen_base_anchors(self):
+        return [self.gen_single_level_base_anchors(b, self.scales, self.ratios, self.angles,
+                                                   None if self.centers is None else self.centers[lvl])
+                for lvl, b in enumerate(self.base_sizes)]
+
+    def gen_single_level_base_anchors(self, base_size, scales, ratios, angles, centers):
+        cx, cy = (self.center_offset * base_size,) * 2 if centers is None else centers
+        ws, hs = _aspect_sides(base_size, ratios, scales, self.scale_major and self.mode == "R")
+        one = torch.ones_like(angles)
+        ws, hs = (ws[:, None] * one[None, :]).reshape(-1), (hs[:, None] * one[None, :]).reshape(-1)
+        cols = [cx - 0.5 * ws, cy - 0.5 * hs, cx + 0.5 * ws, cy + 0.5 * hs]
+        if self.mode == "R":
+            cols.append(angles.repeat(len(scales) * len(ratios)))
+        return torch.stack(cols, dim=-1)
+
+    def single_level_grid_anchors(self, base_anchor, featmap_size, stride=(16, 16), device=None):
+        key = (id(base_anchor), tuple(featmap_size), tuple(stride), str(device))
+        hit = self._lattices.get(key)
+        if hit is None:
+            base = base_anchor if device is None else base_anchor.to(device)
+            hit = self._lattices[key] = _lattice(base, featmap_size[0], featmap_size[1], stride[0], stride[1], (0, 2),
+                                                 (1, 3))
+        return hit
+
+    def grid_anchors(self, featmap_sizes, device=None):
+        assert self.num_levels == len(featmap_sizes)
+        return [self.single_level_grid_anchors(self.base_anchors[lvl], featmap_sizes[lvl], self.strides[lvl], device)
+                for lvl in range(self.num_levels)]
+
+    def single_level_valid_flags(self, featmap_size, valid_size, num_base_anchors, device=None):
+        return _inside(featmap_size[0], featmap_size[1], valid_size[0], valid_size[1], num_base_anchors, device)
+
+    def valid_flags(self, featmap_sizes, pad_shape, device=None):
+        assert self.num_levels == len(featmap_sizes)
+        img_h, img_w = pad_shape[:2]
+        flags = []
+        for lvl, (feat_h, feat_w) in enumerate(featmap_sizes):
+            sx, sy = self.strides[lvl]
+            covered = (min(int(np.ceil(img_h / sy)), feat_h), min(int(np.ceil(img_w / sx)), feat_w))
+            flags.append(self.single_level_valid_flags((feat_h, feat_w), covered, self.num_base_anchors[lvl], device))
+        return flags
+
+
+@BOXES.register_module()
 class AnchorGenerator:
     """Multi-level horizontal anchors <x1, y1, x2, y2> (anchor_generator.py:L198-597): per level a base set around
     `center_offset * base_size` (or an explicit centre), one lattice per feature map."""

@@ -191,3 +191,94 @@ def integral_rows(x, n):
                                            L.stream_ptr(x)), "jdet_dist_integral")
         return out
     return torch.cat([integral(x[:, :4 * k], n), integral_angle(x[:, 4 * k:], n)[:, None]], dim=1)
+
+
+# ---- the horizontal-anchor algebra of RetinaHead (box_ops.py:L36-86, L117-129, L650-675 of the reference) ----------------
+def loc2bbox_r(src_bbox, loc, mean=(0., 0., 0., 0., 0.), std=(1., 1., 1., 1., 1.)):
+    """(n, 5) [x, y, w, h, a] sources + (n, 5) offsets -> (n, 5) boxes, with the reference's (x1 + x2) / 2, x2 - x1
+    round trip through the corners"""
+    if src_bbox.shape[0] == 0:
+        return loc.new_zeros((0, 4))
+    loc = loc * loc.new_tensor(std) + loc.new_tensor(mean)
+    sx, sy, sw, sh = src_bbox[:, 0:1], src_bbox[:, 1:2], src_bbox[:, 2:3], src_bbox[:, 3:4]
+    cx = loc[:, 0:1] * sw + sx
+    cy = loc[:, 1:2] * sh + sy
+    w = torch.exp(loc[:, 2:3]) * sw
+    h = torch.exp(loc[:, 3:4]) * sh
+    x1, y1, x2, y2 = cx - 0.5 * w, cy - 0.5 * h, cx + 0.5 * w, cy + 0.5 * h
+    theta = loc[:, 4:5] + src_bbox[:, 4:5]
+    return torch.cat([(x1 + x2) / 2, (y1 + y2) / 2, x2 - x1, y2 - y1, theta], dim=1)
+
+
+def bbox2loc_r(src_bbox, dst_bbox, mean=(0., 0., 0., 0., 0.), std=(1., 1., 1., 1., 1.)):
+    """offsets that take (n, 5) sources to (n, 5) targets: the +1 on the source sides and eps = 1e-5 inside the logs are
+    the reference's"""
+    x, y, w, h = src_bbox[:, 0:1], src_bbox[:, 1:2], src_bbox[:, 2:3], src_bbox[:, 3:4]
+    bx, by, bw, bh = dst_bbox[:, 0:1], dst_bbox[:, 1:2], dst_bbox[:, 2:3], dst_bbox[:, 3:4]
+    eps = 1e-5
+    dx = (bx - x) / (w + 1)
+    dy = (by - y) / (h + 1)
+    dw = torch.log(bw / (w + 1) + eps)
+    dh = torch.log(bh / (h + 1) + eps)
+    da = dst_bbox[:, 4:5] - src_bbox[:, 4:5]
+    loc = torch.cat([dx, dy, dw, dh, da], dim=1)
+    return (loc - loc.new_tensor(mean)) / loc.new_tensor(std)
+
+
+def bbox_iou(bbox_a, bbox_b):
+    """(A, 4) x (K, 4) corner boxes -> (A, K) IoU: area_i = (br.x - tl.x) * (br.y - tl.y) * [tl < br in both],
+    area_i / (area_a + area_b - area_i).  csrc/retina.hip evaluates the same operations in the same order."""
+    assert bbox_a.shape[1] == 4 and bbox_b.shape[1] == 4
+    if bbox_a.numel() == 0 or bbox_b.numel() == 0:
+        return bbox_a.new_zeros((bbox_a.shape[0], bbox_b.shape[0]))
+    tl = torch.maximum(bbox_a[:, None, :2], bbox_b[:, :2])
+    br = torch.minimum(bbox_a[:, None, 2:], bbox_b[:, 2:])
+    d = br - tl
+    area_i = (d[..., 0] * d[..., 1]) * (tl < br).all(dim=2).to(d.dtype)
+    da, db = bbox_a[:, 2:] - bbox_a[:, :2], bbox_b[:, 2:] - bbox_b[:, :2]
+    area_a, area_b = da[:, 0] * da[:, 1], db[:, 0] * db[:, 1]
+    return area_i / (area_a[:, None] + area_b - area_i)
+
+
+def rotated_box_to_bbox(rotated_boxes):
+    """(n, 5) -> (n, 4) [x0, y0, x1, y1]: the enclosing horizontal box of the four corners"""
+    polys = rotated_box_to_poly(rotated_boxes)
+    xs, ys = polys[:, 0::2], polys[:, 1::2]
+    return torch.stack([xs.min(1).values, ys.min(1).values, xs.max(1).values, ys.max(1).values], dim=1)
+
+
+def boxes_xywh_to_x0y0x1y1(boxes):
+    assert boxes.shape[1] >= 4
+    x, y, w, h = boxes[:, 0], boxes[:, 1], boxes[:, 2], boxes[:, 3]
+    return torch.cat([torch.stack([x - 0.5 * w, y - 0.5 * h, x + 0.5 * w, y + 0.5 * h], dim=1), boxes[:, 4:]], dim=1)
+
+
+def boxes_x0y0x1y1_to_xywh(boxes):
+    assert boxes.shape[1] >= 4
+    x0, y0, x1, y1 = boxes[:, 0], boxes[:, 1], boxes[:, 2], boxes[:, 3]
+    return torch.cat([torch.stack([(x0 + x1) / 2, (y0 + y1) / 2, x1 - x0, y1 - y0], dim=1), boxes[:, 4:]], dim=1)
+
+
+def loc2bbox(src_bbox, loc, mean=(0., 0., 0., 0.), std=(1., 1., 1., 1.)):
+    """(n, 4) corner sources + (n, 4) offsets -> (n, 4) corner boxes (box_ops.py:L5-34)"""
+    if src_bbox.shape[0] == 0:
+        return loc.new_zeros((0, 4))
+    loc = loc * loc.new_tensor(std) + loc.new_tensor(mean)
+    sw, sh = src_bbox[:, 2:3] - src_bbox[:, 0:1], src_bbox[:, 3:4] - src_bbox[:, 1:2]
+    cx = loc[:, 0:1] * sw + (src_bbox[:, 0:1] + 0.5 * sw)
+    cy = loc[:, 1:2] * sh + (src_bbox[:, 1:2] + 0.5 * sh)
+    w, h = torch.exp(loc[:, 2:3]) * sw, torch.exp(loc[:, 3:4]) * sh
+    return torch.cat([cx - 0.5 * w, cy - 0.5 * h, cx + 0.5 * w, cy + 0.5 * h], dim=1)
+
+
+def bbox2loc(src_bbox, dst_bbox, mean=(0., 0., 0., 0.), std=(1., 1., 1., 1.)):
+    """offsets that take (n, 4) corner sources to (n, 4) corner targets (box_ops.py:L88-115)"""
+    w, h = src_bbox[:, 2:3] - src_bbox[:, 0:1], src_bbox[:, 3:4] - src_bbox[:, 1:2]
+    x, y = src_bbox[:, 0:1] + 0.5 * w, src_bbox[:, 1:2] + 0.5 * h
+    bw, bh = dst_bbox[:, 2:3] - dst_bbox[:, 0:1], dst_bbox[:, 3:4] - dst_bbox[:, 1:2]
+    bx, by = dst_bbox[:, 0:1] + 0.5 * bw, dst_bbox[:, 1:2] + 0.5 * bh
+    eps = 1e-5
+    w, h = torch.clamp(w, min=eps), torch.clamp(h, min=eps)
+    loc = torch.cat([(bx - x) / w, (by - y) / h, torch.log(torch.clamp(bw / w, 1e-30, 1e30)),
+                     torch.log(torch.clamp(bh / h, 1e-30, 1e30))], dim=1)      # jt.safe_log
+    return (loc - loc.new_tensor(mean)) / loc.new_tensor(std)

@@ -6,8 +6,10 @@ stride-2 subsampling of the last output.
 
 Own structure: three stages (laterals, top-down merge, levels beyond the backbone's), each its own method; the top-down
 step is ONE fused launch per level on channels-last device maps (`ops/upsample_add.py`: (lateral + upsample(top)) / div,
-instead of an upsampled copy plus an add, and one launch instead of two in backward); other layouts / resampling modes
-take the framework's interpolate."""
+instead of an upsampled copy plus an add, and one launch instead of two in backward), for the nearest rule and for
+`upsample_cfg = dict(mode="bilinear", tf_mode=True)` -- the reference framework's resize, which F.interpolate does not
+have (composed from index gathers on other layouts / devices); every other resampling mode takes the framework's
+interpolate."""
 import torch.nn.functional as F
 from torch import nn
 
@@ -74,6 +76,12 @@ class FPN(nn.Module):
         cfg = self.upsample_cfg
         if cfg.get("mode", "nearest") == "nearest" and "scale_factor" not in cfg and UA.fusable(fine, coarse):
             return UA.upsample_add(fine, coarse, div)
+        if cfg.get("mode") == "bilinear" and cfg.get("tf_mode") is True and set(cfg) == {"mode", "tf_mode"}:
+            # the reference framework's resize rule (F.interpolate has no tf_mode): one fused launch, or the same rule
+            # as index gathers on the CPU / other layouts / a coarse map larger than the fine one
+            if UA.fusable(fine, coarse) and fine.shape[2] >= coarse.shape[2] and fine.shape[3] >= coarse.shape[3]:
+                return UA.upsample_add_bilinear(fine, coarse, div)
+            return UA.upsample_add_bilinear_composed(fine, coarse, div)
         target = {} if "scale_factor" in cfg else {"size": fine.shape[2:]}
         merged = fine + F.interpolate(coarse, **target, **cfg)
         return merged if div == 1 else merged / div

@@ -6,3 +6,4 @@ from .gliding_vertex import GlidingVertex  # noqa: F401
 from .fcos import FCOS, SingleStageDetector  # noqa: F401
 from .h2rbox import H2RBox  # noqa: F401
 from .kd_one_stage import KnowledgeDistillationSingleStageDetector  # noqa: F401
+from .retinanet import RetinaNet  # noqa: F401

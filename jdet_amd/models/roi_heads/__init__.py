@@ -14,3 +14,4 @@ from .h2rbox_head import H2RBoxHead  # noqa: F401
 from .rotated_reppoints_head import MlvlPointGenerator, RotatedRepPointsHead  # noqa: F401
 from .rotated_retina_distribution_head import RotatedRetinaDistributionHead  # noqa: F401
 from .ld_rotated_retina_head import RotatedRetinaLocalizationDistillationHead  # noqa: F401
+from .retina_head import RetinaHead  # noqa: F401

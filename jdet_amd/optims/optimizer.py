@@ -101,6 +101,42 @@ class SGD(_RunnerInterface, torch.optim.SGD):
 
 
 @OPTIMS.register_module()
+class GradMutilpySGD(SGD):
+    """optims/optimizer.py:L39-67 of the reference (its spelling): SGD whose parameter groups may carry
+    `grad_mutilpy = m`; after clipping and before the update the gradients of such a group are multiplied by m
+    (`dp = p * weight_decay + g * m`).  `params` may be tensors or group dicts.  Without a multiplier other than 1 the
+    step is `SGD.step`, bit for bit."""
+
+    def __init__(self, params, grad_clip=None, **kwargs):
+        params = list(params)
+        groups = [g for g in params if isinstance(g, dict)]
+        super().__init__([p for g in groups for p in g["params"]] if groups else params, grad_clip=grad_clip, **kwargs)
+        if groups:
+            # SGD.__init__ decided fused / foreach from all the tensors; rebuild the groups with their own settings
+            base = {k: v for k, v in self.param_groups[0].items() if k != "params"}
+            self.param_groups = []
+            for g in groups:
+                kept = [p for p in g["params"] if p.requires_grad]
+                if kept:
+                    self.add_param_group(dict(base, **{k: v for k, v in g.items() if k != "params"}, params=kept))
+
+    def step(self, loss=None):
+        if all(g.get("grad_mutilpy", 1) == 1 for g in self.param_groups):
+            return super().step(loss)
+        self._backward(loss)
+        if self.grad_clip is not None:
+            self._clip()
+        for g in self.param_groups:
+            m = g.get("grad_mutilpy", 1)
+            grads = [p.grad for p in g["params"] if p.grad is not None]
+            if m != 1 and grads:
+                torch._foreach_mul_(grads, m)
+        if self.fused_step:
+            self._seed_late_momentum()
+        torch.optim.SGD.step(self)
+
+
+@OPTIMS.register_module()
 class AdamW(_RunnerInterface, torch.optim.AdamW):
     """optims/optimizer.py:L75-77 of the reference (Jittor's AdamW under the same `step(loss)` interface): decoupled
     weight decay.  Device fp32 parameters take torch's fused multi-tensor kernel, everything else the foreach form;
