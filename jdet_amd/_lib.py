@@ -197,6 +197,17 @@ RETINA_SIGNATURES = {
     "jdet_upsample_add_bilinear_nhwc_backward": (_i, [_p, _i, _i, _i, _i, _i, _i, _f, _p, _p]),
 }
 
+# mirrors include/jdet_hip_csl.h one to one (tests/test_csl_cpu.py checks it): Circular Smooth Label -- CSLCoder's encode /
+# decode and the angle loss of a level of CSLRRetinaHead; same library, its own header
+_d = ctypes.c_double
+CSL_SIGNATURES = {
+    "jdet_csl_encode": (_i, [_p, _l, _i, _d, _i, _d, _p, _p]),
+    "jdet_csl_decode": (_i, [_p, _l, _p, _l, _i, _d, _p, _p]),
+    "jdet_csl_angle_loss_level": (_i, [_p, _p, _l, _l, _p, _l, _l, _l, _i, _d, _i, _d, _f, _f, _p, _f, _p, _p, _p, _sz,
+                                       _p]),
+}
+CSL_WINDOWS = {"pulse": 0, "rect": 1, "triangle": 2, "gaussian": 3}
+
 _lib = None
 
 # Hull-point ordering inside the rotated IoU: 0 = the reference's CPU path (std::sort,
@@ -227,7 +238,7 @@ def lib():
         # process and our DT_NEEDED entry resolves to that same runtime: one HIP context, shared
         # streams and allocations.
         l = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(RETINA_SIGNATURES.items()):
+        for name, (res, args) in [kv for table in (SIGNATURES, RETINA_SIGNATURES, CSL_SIGNATURES) for kv in table.items()]:
             fn = getattr(l, name)  # AttributeError here == ABI drift: fail loudly
             fn.restype = res
             fn.argtypes = args

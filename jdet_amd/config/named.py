@@ -346,6 +346,14 @@ LD_RETINANET_CFG["model"] = dict(LD_RETINANET_CFG["model"], type="KnowledgeDisti
                                  teacher_config=DIST_RETINANET_R50_CFG, teacher_ckpt=None)
 
 
+# ---- Circular Smooth Label (projects/csl/configs/rotated_retinanet_obb_csl_gaussian_r50_fpn_1x_dota.py): RetinaNet-OBB
+# on R50 whose angle is classified into 45 bins of 4 degrees under a gaussian window of radius 3.
+# tests/golden/configs/rotated_retinanet_obb_csl_gaussian_r50_fpn_1x_dota.yaml holds it as `Config` reads it.
+CSL_RETINANET_CFG = _ld_retinanet_cfg(
+    "CSLRRetinaHead", backbone="Resnet50", angle_coder=dict(type="CSLCoder", omega=4, window="gaussian", radius=3),
+    loss_angle=dict(type="SmoothFocalLoss", gamma=2.0, alpha=0.25, loss_weight=0.8))
+
+
 # ---- the reference's own RetinaNet (configs/retinanet_r50v1d_fpn_{dota,dota1_5,fair}.py): Resnet50_v1d, a bilinear FPN
 # merge halved at every step, RetinaHead on 21 horizontal anchors per location.  The three files differ in n_class only
 # (dota1_5 says 15, as dota does).  tests/golden/configs/retinanet_r50v1d_fpn_*.yaml hold them as `Config` reads them.

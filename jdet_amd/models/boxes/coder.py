@@ -1,6 +1,7 @@
 """BBox coders of the named configs.  Mirrors python/jdet/models/boxes/coder.py:
 `DeltaXYWHABBoxCoder` L76-141."""
 import math
+import os
 
 import torch
 
@@ -418,3 +419,88 @@ class GVDeltaXYWHBBoxCoder:
                                                  max_h, max_w, L.ptr(out), L.stream_ptr(d)), "jdet_gv_delta_decode")
             return out
         return gv_delta_decode(bboxes, pred_bboxes, self.means, self.stds, max_shape, wh_ratio_clip)
+
+
+# the fused routes of Circular Smooth Label: CSLCoder's kernels, the angle-loss node and the head's in-place decode
+# (A/B switch; profiles/csl.md).  Read at call time.
+CSL_FUSED = os.environ.get("JDET_CSL_FUSED", "1") != "0"
+
+
+@BOXES.register_module()
+class CSLCoder:
+    """Circular Smooth Label coder (coder.py:L521-605 of the reference): an angle delta becomes a smooth label over
+    `coding_len = int(180 // omega)` bins, a row of bin scores becomes the angle of its best bin.  include/jdet_hip_csl.h
+    states the rules; two of them are this project's:
+
+      * the bin of a target is evaluated in float32 in the reference's operation order, whatever the input's dtype;
+      * where the reference scatters several values into one bin (gaussian window, coding_len < 180: the winner of its
+        duplicate indices is undefined) the LARGEST wins, i.e. the label is exp(-d^2 / (2 radius^2)) of the circular bin
+        distance d.  rect / triangle windows wider than the code (2 radius > coding_len) are refused.
+
+    omega: degrees per bin, int or float; radius: int for 'triangle' / 'rect', any positive number for 'gaussian'."""
+
+    def __init__(self, omega=1, window="gaussian", radius=6):
+        assert window in ["gaussian", "triangle", "rect", "pulse"]
+        self.angle_range = 180
+        self.angle_offset = 45
+        self.omega = omega
+        self.window = window
+        self.radius = radius
+        self.coding_len = int(self.angle_range // omega)
+        if self.coding_len < 1:
+            raise ValueError("omega=%r leaves no bin" % (omega,))
+        if window in ("rect", "triangle") and (radius != int(radius) or radius < 1 or 2 * radius > self.coding_len):
+            raise ValueError("a '%s' window of radius %r does not fit %d bins (an integer radius, 2 * radius <= coding_len)"
+                             % (window, radius, self.coding_len))
+        if window == "gaussian" and not radius > 0:
+            raise ValueError("a gaussian window needs radius > 0, got %r" % (radius,))
+
+    def bins(self, angle_targets):
+        """(n, 1) angle deltas -> (n, 1) int64 bins in [0, coding_len): float32, the reference's operation order, truncated
+        toward zero, floor-mod.  The divisor is a tensor: the framework divides by a host scalar through its reciprocal."""
+        a = angle_targets.float()
+        deg = (a * (180 / math.pi) + self.angle_offset) / a.new_full((), self.omega)
+        return deg.long() % self.coding_len
+
+    def encode(self, angle_targets):
+        """(n, 1) -> (n, coding_len) labels of angle_targets' dtype"""
+        assert angle_targets.dim() == 2 and angle_targets.shape[1] == 1
+        n, Lc = angle_targets.shape[0], self.coding_len
+        if CSL_FUSED and Lc <= 180 and _fused32_ok(angle_targets) and n > 0:
+            a = L.f32c(angle_targets)
+            out = torch.empty((n, Lc), dtype=torch.float32, device=a.device)
+            L.check(L.lib().jdet_csl_encode(L.ptr(a), n, Lc, float(self.omega), L.CSL_WINDOWS[self.window],
+                                            float(self.radius), L.ptr(out), L.stream_ptr(a)), "jdet_csl_encode")
+            return out
+        dtype = angle_targets.dtype if angle_targets.is_floating_point() else torch.float32
+        d = (torch.arange(Lc, device=angle_targets.device)[None, :] - self.bins(angle_targets)) % Lc
+        r = self.radius
+        if self.window == "pulse":
+            y = (d == 0).double()
+        elif self.window == "rect":
+            y = ((d < r) | (d >= Lc - r)).double()
+        elif self.window == "triangle":
+            b = torch.where(d < r, d, Lc - d)
+            y = torch.where(b <= r, 1.0 - b.double() / r, torch.zeros((), dtype=torch.float64, device=d.device))
+        else:
+            cd = torch.minimum(d, Lc - d).double()
+            y = torch.exp(-(cd * cd) / (2 * r ** 2))
+        return y.to(dtype)
+
+    def decode(self, angle_preds, index=None):
+        """(rows, coding_len) bin scores -> the angle of the first best bin of every row, or of the rows `index` (int64)
+        names: (n,) of angle_preds' dtype.  On the fused route the rows are read in place (jdet_csl_decode)."""
+        assert angle_preds.dim() == 2 and angle_preds.shape[1] == self.coding_len
+        n = angle_preds.shape[0] if index is None else index.shape[0]
+        if (CSL_FUSED and self.coding_len <= 180 and _fused32_ok(angle_preds) and angle_preds.is_contiguous() and n > 0 and
+                (index is None or (index.is_cuda and index.dtype == torch.int64 and index.dim() == 1))):
+            out = torch.empty((n,), dtype=torch.float32, device=angle_preds.device)
+            idx = index.contiguous() if index is not None else None
+            L.check(L.lib().jdet_csl_decode(L.ptr(angle_preds), angle_preds.shape[0], L.ptr(idx), n, self.coding_len,
+                                            float(self.omega), L.ptr(out), L.stream_ptr(angle_preds)), "jdet_csl_decode")
+            return out
+        if index is not None:
+            angle_preds = angle_preds[index]
+        idx = angle_preds.argmax(dim=1)
+        angle = ((idx.double() + 0.5) * self.omega) % self.angle_range - self.angle_offset
+        return (angle * (math.pi / 180)).to(angle_preds.dtype)

@@ -8,3 +8,4 @@ from .convex_giou_loss import ConvexGIoULoss  # noqa: F401
 from .iou_loss import IoULoss, iou_loss  # noqa: F401
 from .h2rbox_loss import H2RBoxLoss  # noqa: F401
 from .kd_loss import IMLoss, KnowledgeDistillationKLDivLoss  # noqa: F401
+from .smooth_focal_loss import SmoothFocalLoss  # noqa: F401

@@ -15,3 +15,4 @@ from .rotated_reppoints_head import MlvlPointGenerator, RotatedRepPointsHead  # 
 from .rotated_retina_distribution_head import RotatedRetinaDistributionHead  # noqa: F401
 from .ld_rotated_retina_head import RotatedRetinaLocalizationDistillationHead  # noqa: F401
 from .retina_head import RetinaHead  # noqa: F401
+from .csl_rretina_head import CSLRRetinaHead  # noqa: F401

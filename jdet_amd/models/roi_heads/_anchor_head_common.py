@@ -54,10 +54,12 @@ class RotatedAnchorHeadMixin:
     anchor_target = staticmethod(anchor_target)     # (RotatedATSSHead: its own, the level sizes go to the assigner)
 
     def _stage_loss(self, cls_scores, bbox_preds, anchor_list, valid_flag_list, gt_bboxes, gt_labels, img_metas,
-                    gt_bboxes_ignore, cfg, loss_cls_fn, loss_bbox_fn, targets=None, need_anchors=True):
+                    gt_bboxes_ignore, cfg, loss_cls_fn, loss_bbox_fn, targets=None, need_anchors=True, extra_preds=()):
         """(losses_cls, losses_bbox) per level of one stage, None where the targets are.  targets: what
         `self.anchor_target` returned for these anchors, else computed here; need_anchors: the per-level anchors, which
-        the loss only reads where it regresses decoded boxes"""
+        the loss only reads where it regresses decoded boxes; extra_preds: further per-level prediction lists, handed to
+        `_loss_single` behind the level's bbox_weights (CSLRRetinaHead: the angle classification maps, and a third loss
+        list comes back)"""
         num_level_anchors = [anchors.size(0) for anchors in anchor_list[0]]
         all_anchor_list = [None] * len(num_level_anchors)
         if need_anchors:
@@ -74,7 +76,8 @@ class RotatedAnchorHeadMixin:
         labels_list, label_weights_list, bbox_targets_list, bbox_weights_list, num_total_pos, num_total_neg = targets
         num_total_samples = num_total_pos + num_total_neg if self.sampling else num_total_pos
         return multi_apply(self._loss_single, cls_scores, bbox_preds, all_anchor_list, labels_list, label_weights_list,
-                           bbox_targets_list, bbox_weights_list, loss_cls_fn=loss_cls_fn, loss_bbox_fn=loss_bbox_fn,
+                           bbox_targets_list, bbox_weights_list, *extra_preds, loss_cls_fn=loss_cls_fn,
+                           loss_bbox_fn=loss_bbox_fn,
                            num_total_samples=num_total_samples, cfg=cfg)
 
     def _loss_single(self, cls_score, bbox_pred, anchors, labels, label_weights, bbox_targets, bbox_weights,

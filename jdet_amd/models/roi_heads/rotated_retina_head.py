@@ -72,8 +72,8 @@ class RotatedRetinaHead(RotatedAnchorHeadMixin, nn.Module):
         normal_init(self.retina_reg, std=0.01)
         normal_init(self.retina_cls, std=0.01, bias=bias_cls)
 
-    def forward_single(self, x, stride=None, mask=None):
-        """mask: set when x is a LevelPack of several small levels (models/utils/level_pack.py)"""
+    def _towers(self, x, mask=None):
+        """(cls_feat, reg_feat); mask: set when x is a LevelPack of several small levels (models/utils/level_pack.py)"""
         reg_feat = cls_feat = x
         for conv in self.reg_convs:
             reg_feat = conv(reg_feat)
@@ -83,6 +83,10 @@ class RotatedRetinaHead(RotatedAnchorHeadMixin, nn.Module):
             cls_feat = conv(cls_feat)
             if mask is not None:
                 cls_feat = cls_feat * mask
+        return cls_feat, reg_feat
+
+    def forward_single(self, x, stride=None, mask=None):
+        cls_feat, reg_feat = self._towers(x, mask)
         return conv_module(self.retina_cls, cls_feat), conv_module(self.retina_reg, reg_feat)
 
     def loss(self, cls_scores, bbox_preds, gt_bboxes, gt_labels, img_metas, gt_bboxes_ignore=None):
