@@ -13,8 +13,15 @@
 // the three half planes of the second triangle (<= 6 vertices) and measured with the shoelace formula.
 // mode 0: the reference kernel's degenerate rule (union == 0 -> (inter + 1) / (union + 1));
 // mode 1: `iou_poly`'s rule (inter / max(union, 0.01)).
-// Parity: unpinned by reference execution (CUDA-only source, no fixtures; shapely is not installed here) -- the tests
-// hold this kernel to a float64 restatement of the same definition and to closed-form areas (tests/test_gpu_poly.py).
+// Parity: unpinned by reference execution (CUDA-only source, no fixtures; shapely is not installed here).  The kernel
+// is held instead to an exact rational evaluation of the definition on the same float32 inputs, by a method that
+// shares nothing with this one (vertical slabs, oracle/poly_exact.py), within
+//   K * 2^-24 * R2 / max(union, floor) + 2^-23,   K = 1471 counted from the roundings below (tests/poly_cases.py),
+// R2 the largest squared distance of the 8 vertices from their mean -- over every contact regime (shared, partly
+// shared and collinear edges, vertex on edge / vertex, containment, the fan centre on a vertex or an edge, repeated
+// vertices, zero area, darts, slivers, near-identical and tiny polygons), both windings, every cyclic relabeling,
+// both pair orders, at the origin and at (4000, 2000): tests/test_gpu_poly_regimes.py; tests/test_gpu_poly.py keeps
+// the float64 restatement (oracle/poly_oracle.py, itself checked against the exact evaluation) and closed forms.
 #include "common.h"
 #include "nms_scan.h"
 
@@ -107,7 +114,9 @@ __device__ float poly_iou(const float* __restrict__ pa, const float* __restrict_
         inter += fan_pair(a, b, c, d);
       }
     }
-    inter = fmaxf(inter, 0.f);
+    // an intersection is no larger than either polygon: without the upper clamp the rounding of the interpolated
+    // vertices can leave inter > a1 + a2 for two crossing zero-area quads, a negative union and an IoU of -1
+    inter = fminf(fmaxf(inter, 0.f), fminf(a1, a2));
   }
   const float uni = a1 + a2 - inter;
   if (mode == 1) return inter / fmaxf(uni, 0.01f);

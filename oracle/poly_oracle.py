@@ -5,8 +5,15 @@ decomposition) and a CPU function `iou_poly` (L247-252) that calls shapely -- wh
 kernel has no CPU source, so neither can be executed: PARITY UNPINNED by reference execution.  This file restates the
 DEFINITION (area of the intersection of two simple 4-point polygons over the area of their union) two independent
 ways -- direct Sutherland-Hodgman clipping for convex polygons, and the signed fan-triangle sum for any simple
-polygon -- checks them against each other and against closed-form areas (tests/test_poly_oracle.py), and is what the
-HIP kernel is held to.
+polygon -- and checks them against each other and against closed-form areas (tests/test_poly_oracle.py).
+
+Both routines share their algorithm (clip_left, its `>= 0` and strict-crossing rules, the fan, the orientation
+handling) with csrc/poly_iou.hip, so agreement with the kernel alone would not show a mistake in any of those.  What
+pins the arithmetic is oracle/poly_exact.py: an exact rational evaluation by vertical slabs that shares nothing with
+clipping or fans.  This file is held to it on simple quadrilaterals in general position, within the float64 form of
+the rounding count of tests/poly_cases.py (tests/test_poly_exact_cpu.py); the HIP kernel is held to it directly, on
+the same float32 inputs, in every contact regime (tests/test_gpu_poly_regimes.py), and to this file on random
+quadrilaterals (tests/test_gpu_poly.py).  Self-intersecting input is outside the definition on all sides.
 """
 import numpy as np
 
