@@ -208,6 +208,21 @@ CSL_SIGNATURES = {
 }
 CSL_WINDOWS = {"pulse": 0, "rect": 1, "triangle": 2, "gaussian": 3}
 
+# mirrors include/jdet_hip_lsk.h one to one (tests/test_lsk_cpu.py checks it): the channels-last depthwise convolution
+# (forward = data gradient on flipped weights, GELU backward, two-stage weight gradient) and the kernel-selection step
+# of the LSKNet backbones; same library, its own header
+LSK_SIGNATURES = {
+    "jdet_dwconv_nhwc_forward": (_i, [_p, _p, _p] + [_i] * 11 + [_p, _p]),
+    "jdet_dwconv_nhwc_wgrad_workspace": (_sz, [_i] * 6),
+    "jdet_dwconv_nhwc_wgrad": (_i, [_p, _p] + [_i] * 10 + [_p, _p, _p, _sz, _p]),
+    "jdet_dwconv_gelu_backward": (_i, [_p, _p, _p, _p] + [_i] * 10 + [_p, _p]),
+    "jdet_lsk_squeeze_forward": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _p]),
+    "jdet_lsk_squeeze_backward": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _p]),
+    "jdet_lsk_select_forward": (_i, [_p, _p, _p, _i, _i, _i, _i, _p, _p]),
+    "jdet_lsk_select_backward": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p]),
+}
+DWCONV_ACTS = {None: 0, "none": 0, "gelu": 1}
+
 _lib = None
 
 # Hull-point ordering inside the rotated IoU: 0 = the reference's CPU path (std::sort,
@@ -238,7 +253,8 @@ def lib():
         # process and our DT_NEEDED entry resolves to that same runtime: one HIP context, shared
         # streams and allocations.
         l = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in [kv for table in (SIGNATURES, RETINA_SIGNATURES, CSL_SIGNATURES) for kv in table.items()]:
+        for name, (res, args) in [kv for table in (SIGNATURES, RETINA_SIGNATURES, CSL_SIGNATURES, LSK_SIGNATURES)
+                                          for kv in table.items()]:
             fn = getattr(l, name)  # AttributeError here == ABI drift: fail loudly
             fn.restype = res
             fn.argtypes = args
