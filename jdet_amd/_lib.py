@@ -223,6 +223,13 @@ LSK_SIGNATURES = {
 }
 DWCONV_ACTS = {None: 0, "none": 0, "gelu": 1}
 
+# mirrors include/jdet_hip_strip.h one to one (tests/test_strip_cpu.py checks it): the rolling-window 1 x K / K x 1
+# depthwise convolution of the StripNet backbones (forward = data gradient on flipped weights); same library, its own
+# header
+STRIP_SIGNATURES = {
+    "jdet_strip_conv_forward": (_i, [_p, _p, _p] + [_i] * 6 + [_p, _p]),
+}
+
 _lib = None
 
 # Hull-point ordering inside the rotated IoU: 0 = the reference's CPU path (std::sort,
@@ -253,8 +260,8 @@ def lib():
         # process and our DT_NEEDED entry resolves to that same runtime: one HIP context, shared
         # streams and allocations.
         l = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in [kv for table in (SIGNATURES, RETINA_SIGNATURES, CSL_SIGNATURES, LSK_SIGNATURES)
-                                          for kv in table.items()]:
+        for name, (res, args) in [kv for table in (SIGNATURES, RETINA_SIGNATURES, CSL_SIGNATURES, LSK_SIGNATURES,
+                                                   STRIP_SIGNATURES) for kv in table.items()]:
             fn = getattr(l, name)  # AttributeError here == ABI drift: fail loudly
             fn.restype = res
             fn.argtypes = args

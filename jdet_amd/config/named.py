@@ -474,3 +474,98 @@ LSKNET_S_ORCNN_CFG = {'model': {'type': 'OrientedRCNN',
                'warmup_iters': 500,
                'warmup_ratio': 0.001,
                'milestones': [7, 10]}}
+
+
+# configs/strip_rcnn_s_fpn_1x_dota_with_flip.py:L2-197 -- Strip R-CNN: a StripNet_S backbone, OrientedRPNHead and a StripHead
+# under AdamW: the model, optimizer and scheduler sections as `Config` reads them
+# (tests/golden/configs/strip_rcnn_s_fpn_1x_dota_with_flip.yaml).  `reg_class_agnostic` is what the file says; StripHead,
+# like the reference, regresses per class whatever it says (models/roi_heads/strip_head.py).  Where the `pretrained` file
+# is absent the init stays in place.
+STRIP_RCNN_S_CFG = {'model': {'type': 'StripRCNN',
+           'backbone': {'type': 'StripNet_S',
+                        'img_size': 1024,
+                        'num_stages': 4,
+                        'out_indices': [0, 1, 2, 3],
+                        'pretrained': './weights/stripnet_s_jittor.pkl'},
+           'neck': {'type': 'FPN', 'in_channels': [64, 128, 320, 512], 'out_channels': 256, 'num_outs': 5},
+           'rpn': {'type': 'OrientedRPNHead',
+                   'in_channels': 256,
+                   'num_classes': 1,
+                   'min_bbox_size': 0,
+                   'nms_thresh': 0.8,
+                   'nms_pre': 2000,
+                   'nms_post': 2000,
+                   'feat_channels': 256,
+                   'bbox_type': 'obb',
+                   'reg_dim': 6,
+                   'background_label': 0,
+                   'reg_decoded_bbox': False,
+                   'pos_weight': -1,
+                   'anchor_generator': {'type': 'AnchorGenerator',
+                                        'scales': [8],
+                                        'ratios': [0.5, 1.0, 2.0],
+                                        'strides': [4, 8, 16, 32, 64]},
+                   'bbox_coder': {'type': 'MidpointOffsetCoder',
+                                  'target_means': [0.0, 0.0, 0.0, 0.0, 0.0, 0.0],
+                                  'target_stds': [1.0, 1.0, 1.0, 1.0, 0.5, 0.5]},
+                   'loss_cls': {'type': 'CrossEntropyLossForRcnn', 'use_sigmoid': True, 'loss_weight': 1.0},
+                   'loss_bbox': {'type': 'SmoothL1Loss', 'beta': 0.1111111111111111, 'loss_weight': 1.0},
+                   'assigner': {'type': 'MaxIoUAssigner',
+                                'pos_iou_thr': 0.7,
+                                'neg_iou_thr': 0.3,
+                                'min_pos_iou': 0.3,
+                                'ignore_iof_thr': -1,
+                                'match_low_quality': True,
+                                'assigned_labels_filled': -1},
+                   'sampler': {'type': 'RandomSampler',
+                               'num': 256,
+                               'pos_fraction': 0.5,
+                               'neg_pos_ub': -1,
+                               'add_gt_as_proposals': False}},
+           'bbox_head': {'type': 'StripHead',
+                         'num_classes': 15,
+                         'in_channels': 256,
+                         'fc_out_channels': 1024,
+                         'score_thresh': 0.05,
+                         'assigner': {'type': 'MaxIoUAssigner',
+                                      'pos_iou_thr': 0.5,
+                                      'neg_iou_thr': 0.5,
+                                      'min_pos_iou': 0.5,
+                                      'ignore_iof_thr': -1,
+                                      'match_low_quality': False,
+                                      'assigned_labels_filled': -1,
+                                      'iou_calculator': {'type': 'BboxOverlaps2D_rotated_v1'}},
+                         'sampler': {'type': 'RandomSamplerRotated',
+                                     'num': 512,
+                                     'pos_fraction': 0.25,
+                                     'neg_pos_ub': -1,
+                                     'add_gt_as_proposals': True},
+                         'bbox_coder': {'type': 'OrientedDeltaXYWHTCoder',
+                                        'target_means': [0.0, 0.0, 0.0, 0.0, 0.0],
+                                        'target_stds': [0.1, 0.1, 0.2, 0.2, 0.1]},
+                         'bbox_roi_extractor': {'type': 'OrientedSingleRoIExtractor',
+                                                'roi_layer': {'type': 'ROIAlignRotated_v1',
+                                                              'output_size': 7,
+                                                              'sampling_ratio': 2},
+                                                'out_channels': 256,
+                                                'extend_factor': [1.4, 1.2],
+                                                'featmap_strides': [4, 8, 16, 32]},
+                         'loss_cls': {'type': 'CrossEntropyLoss'},
+                         'loss_bbox': {'type': 'SmoothL1Loss', 'beta': 1.0, 'loss_weight': 1.0},
+                         'with_bbox': True,
+                         'with_shared_head': False,
+                         'with_avg_pool': False,
+                         'with_cls': True,
+                         'with_reg': True,
+                         'start_bbox_type': 'obb',
+                         'end_bbox_type': 'obb',
+                         'reg_dim': None,
+                         'reg_class_agnostic': True,
+                         'reg_decoded_bbox': False,
+                         'pos_weight': -1}},
+ 'optimizer': {'type': 'AdamW', 'lr': 0.0001, 'betas': [0.9, 0.999], 'weight_decay': 0.05},
+ 'scheduler': {'type': 'StepLR',
+               'warmup': 'linear',
+               'warmup_iters': 500,
+               'warmup_ratio': 0.001,
+               'milestones': [7, 10]}}

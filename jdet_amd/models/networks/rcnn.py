@@ -30,3 +30,9 @@ class RCNN(nn.Module):
 @MODELS.register_module()
 class OrientedRCNN(RCNN):
     """https://openaccess.thecvf.com/content/ICCV2021/papers/Xie_Oriented_R-CNN_for_Object_Detection_ICCV_2021_paper.pdf"""
+
+
+@MODELS.register_module()
+class StripRCNN(RCNN):
+    """Strip R-CNN (python/jdet/models/networks/strip_rcnn.py): the two-stage wrapper over a StripNet backbone, an
+    OrientedRPNHead and a StripHead"""

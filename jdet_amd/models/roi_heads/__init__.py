@@ -16,3 +16,4 @@ from .rotated_retina_distribution_head import RotatedRetinaDistributionHead  # n
 from .ld_rotated_retina_head import RotatedRetinaLocalizationDistillationHead  # noqa: F401
 from .retina_head import RetinaHead  # noqa: F401
 from .csl_rretina_head import CSLRRetinaHead  # noqa: F401
+from .strip_head import StripHead  # noqa: F401

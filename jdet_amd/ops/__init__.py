@@ -6,6 +6,6 @@ everything else is reached as a submodule (`from jdet.ops import roi_align_rotat
 `from jdet.ops.nms_rotated import multiclass_nms_rotated`, ...).
 """
 from . import (dcn_v1, dwconv, lsk_select, nms_rotated, orn, riroi_align, roi_align,  # noqa: F401
-               roi_align_rotated, roi_align_rotated_v1)
+               roi_align_rotated, roi_align_rotated_v1, strip_conv)
 from .box_iou_rotated import box_iou_rotated  # noqa: F401
 from .box_iou_rotated_v1 import box_iou_rotated_v1  # noqa: F401
